@@ -12,7 +12,20 @@ by ~25 ms of untimed scratch copies (`preheat`, `preheat_ms` on the line):
 the GPU's clocks ramp back only tens of ms after it idles, which otherwise
 slows the first milliseconds of a short timed region by up to 8 %.
 
-Also reported on the same JSON line:
+A plain run does only that: set up, W warmup steps, the bit check, the K
+timed steps, the outputs if --dump-outputs is given, the line.  On the line,
+`ms_per_step` is the wall time of one timed step in milliseconds, and the
+keys of the legs below are null.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of
+the path receives it: DIR/encoded.npy (the characters), DIR/decoded.npy (the
+bytes decoded back) and DIR/decode_result.npy (out_len, valid, tail_n of the
+decode's result record), float32 / float64.  Of the two 1 GiB-scale arrays a
+fixed sample is kept (the first and last 65,536 elements whole and seeded
+random positions between them, DUMP_ELEMS each); the inputs are the same
+splitmix64 stream on every run, so two builds can be compared file by file.
+
+With --full, also reported on the same JSON line:
   roofline      the dominant kernel's algorithmic bytes per launch
                 (N + 4*ceil(N/3): read + write) / its average launch time
                 from HIP events (a second pass of the K steps right after
@@ -45,7 +58,8 @@ Also reported on the same JSON line:
                 and the staged form (H2D, kernel, D2H on k streams); bit-
                 checked; never `value`.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                        [--full]
         N > 1 without WORLD_SIZE in the environment: bench.py starts
         `python -m torch.distributed.run --nproc-per-node N` itself (before
         touching the GPU) and relays its line; every rank checks that the
@@ -77,6 +91,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, default=1 << 30, help="bytes per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (roofline, CPU baselines, batch, host, "
+                         "MIME, config 5); the --no-* options select among them")
     ap.add_argument("--cpu-sample", type=int, default=512 << 20,
                     help="bytes of the CPU baseline sample (rank 0, N=1)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -239,6 +258,11 @@ def bench_single(args, world, rank, b64):
     wall = time.perf_counter() - t0
     wall = max_over_ranks(wall, world)
     gpu_ms = ev0.elapsed_time(ev1) / K
+    out = {"N": N, "E": E, "K": K, "wall": wall, "gpu_ms_per_step": gpu_ms}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, enc[:E], b64.Decoded(dec, res))
+    if not args.full:
+        return out
     evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(K)]
     for k in range(K):
         evs[k][0].record(stream)
@@ -249,9 +273,44 @@ def bench_single(args, world, rank, b64):
     torch.cuda.synchronize()
     enc_ms = [evs[k][0].elapsed_time(evs[k][1]) for k in range(K)]
     dec_ms = [evs[k][1].elapsed_time(evs[k][2]) for k in range(K)]
-    return {"N": N, "E": E, "K": K, "wall": wall, "gpu_ms_per_step": gpu_ms,
-            "enc_ms": statistics.mean(enc_ms), "dec_ms": statistics.mean(dec_ms),
-            "enc_ms_min": min(enc_ms), "dec_ms_min": min(dec_ms)}
+    out.update({"enc_ms": statistics.mean(enc_ms), "dec_ms": statistics.mean(dec_ms),
+                "enc_ms_min": min(enc_ms), "dec_ms_min": min(dec_ms)})
+    return out
+
+
+DUMP_ELEMS = 4 << 20  # elements kept of each large output (float32: 16 MiB a file)
+DUMP_EDGE = 1 << 16   # of which the first and the last this many, whole
+
+
+def dump_sample(t: torch.Tensor, seed: int):
+    """`t` as float32 on the host: whole if it has at most DUMP_ELEMS
+    elements, else its first and last DUMP_EDGE elements and the elements at
+    seeded random positions between them (sorted; the same positions on every
+    run for a given length)."""
+    import numpy as np
+
+    n = t.numel()
+    if n > DUMP_ELEMS:
+        inner = np.random.default_rng(seed).integers(DUMP_EDGE, n - DUMP_EDGE,
+                                                     DUMP_ELEMS - 2 * DUMP_EDGE)
+        idx = np.concatenate([np.arange(DUMP_EDGE), np.sort(inner),
+                              np.arange(n - DUMP_EDGE, n)])
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(dirname, rank, chars, decoded):
+    """--dump-outputs: the last timed step's outputs as .npy files (rank 0's
+    under the plain names, rank r's as <name>.rank<r>.npy)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    info = decoded.info()
+    arrays = {"encoded": dump_sample(chars, 0x5EED),
+              "decoded": dump_sample(decoded.out[:info.out_len], 0x5EED + 1),
+              "decode_result": np.array([info.out_len, info.valid, info.tail_n], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + (f".rank{rank}" if rank else "") + ".npy"), a)
 
 
 def bench_batch(args, world, rank, b64, total_buf=1 << 20, L=1024, name="cfg4"):
@@ -1087,6 +1146,50 @@ def launch_ranks(args) -> int:
     return subprocess.call(cmd)
 
 
+def per_kernel_figures(r, ceiling, full):
+    """The line's per-kernel keys: from bench_single's second pass (HIP events
+    around each call), the copy ceilings and the committed PMC summary with
+    --full; null in a plain run, which makes none of these measurements."""
+    if not full:
+        return dict.fromkeys(("encode_ms", "decode_ms", "encode_GBps", "decode_GBps",
+                              "roundtrip_hbm_frac", "roofline"))
+    N = r["N"]
+    per_launch = N + r["E"]  # algorithmic bytes per launch (read + write)
+    dom = "encode" if r["enc_ms"] >= r["dec_ms"] else "decode"
+    dom_ms = max(r["enc_ms"], r["dec_ms"])
+    achieved = per_launch / (dom_ms * 1e-3) / 1e9
+    knames = ["k_encode_flat"] if dom == "encode" else \
+        ["k_decode_probe", "k_decode_lines", "k_decode_suffix_held"]
+    return {
+        "encode_ms": r["enc_ms"],
+        "decode_ms": r["dec_ms"],
+        "encode_GBps": per_launch / (r["enc_ms"] * 1e-3) / 1e9,
+        "decode_GBps": per_launch / (r["dec_ms"] * 1e-3) / 1e9,
+        "roundtrip_hbm_frac": 2 * per_launch / ((r["enc_ms"] + r["dec_ms"]) * 1e-3)
+                              / (HBM_PEAK_GBS * 1e9),
+        "roofline": {
+            "bound": "hbm",
+            "kernel": "+".join(knames),
+            "timing": "HIP events around each b64x call on its stream, mean over a second "
+                      "pass of the K steps right after the timed region (events inside it "
+                      "would add ~7 us of GPU idle per event)",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "copy_ceiling_GBps": ceiling[dom]["GBps"] if ceiling else None,
+            "frac_of_copy": achieved / ceiling[dom]["GBps"] if ceiling else None,
+            "frac_of_copy_per_leg": {
+                "encode": per_launch / (r["enc_ms"] * 1e-3) / 1e9 / ceiling["encode"]["GBps"],
+                "decode": per_launch / (r["dec_ms"] * 1e-3) / 1e9 / ceiling["decode"]["GBps"],
+            } if ceiling else None,
+            "copy_ceiling": ceiling,
+            # the committed PMC summary is for the 1 GiB workload
+            "traffic": load_traffic(knames) if N == 1 << 30 else None,
+        },
+    }
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1134,35 +1237,31 @@ def main():
     b64.device_check()
     placement = bench_placement(b64)
     r = bench_single(args, world, rank, b64)
-    ceiling = copy_ceilings(r["N"], r["E"]) if rank == 0 else None
-    batch = None if args.no_batch else bench_batch(args, world, rank, b64)
-    batch3 = None if args.no_batch else bench_batch(args, world, rank, b64, 1 << 16, 4096,
-                                                    "cfg3")
-    scatter = bench_root_scatter(world, rank)
+    full = args.full  # every leg but the headline's timed steps runs only with --full
+    ceiling = copy_ceilings(r["N"], r["E"]) if full and rank == 0 else None
+    batch = None if not full or args.no_batch else bench_batch(args, world, rank, b64)
+    batch3 = None if not full or args.no_batch else bench_batch(args, world, rank, b64, 1 << 16,
+                                                                4096, "cfg3")
+    scatter = bench_root_scatter(world, rank) if full else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args, b64)
     host = None
-    if rank == 0 and not args.no_host:
+    if full and rank == 0 and not args.no_host:
         host = bench_host_inclusive(args, b64)
     hostfd = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if full and rank == 0 and world == 1 and not args.no_host:
         hostfd = bench_host_fd(args, b64)
     mime = None
-    if rank == 0 and world == 1 and not args.no_mime and args.size == 1 << 30:
+    if full and rank == 0 and world == 1 and not args.no_mime and args.size == 1 << 30:
         mime = bench_mime(args, b64)
     cfg5 = None
-    if not args.no_cfg5 and (world > 1 or not args.no_cpu):
+    if full and not args.no_cfg5 and (world > 1 or not args.no_cpu):
         cfg5 = bench_cfg5(args, world, rank)
 
     if rank == 0:
         N, E, K = r["N"], r["E"], r["K"]
         per_launch = N + E  # algorithmic bytes per launch (read + write)
-        dom = "encode" if r["enc_ms"] >= r["dec_ms"] else "decode"
-        dom_ms = max(r["enc_ms"], r["dec_ms"])
-        achieved = per_launch / (dom_ms * 1e-3) / 1e9
-        knames = ["k_encode_flat"] if dom == "encode" else \
-            ["k_decode_probe", "k_decode_lines", "k_decode_suffix_held"]
         out = {
             "metric": METRIC,
             "value": world * N * K / r["wall"] / 2**30,
@@ -1186,37 +1285,14 @@ def main():
             },
             "gpu_ms_per_step": r["gpu_ms_per_step"],
             "preheat_ms": PREHEAT_MS,
-            "encode_ms": r["enc_ms"],
-            "decode_ms": r["dec_ms"],
-            "encode_GBps": per_launch / (r["enc_ms"] * 1e-3) / 1e9,
-            "decode_GBps": per_launch / (r["dec_ms"] * 1e-3) / 1e9,
-            "roundtrip_hbm_frac": 2 * per_launch / ((r["enc_ms"] + r["dec_ms"]) * 1e-3)
-                                  / (HBM_PEAK_GBS * 1e9),
             # the headline fraction: both legs' algorithmic bytes over the
             # timed region's own GPU time per step (HIP events around the K
             # steps, nothing between them)
             "timed_region_frac": 2 * per_launch / (r["gpu_ms_per_step"] * 1e-3)
                                  / (HBM_PEAK_GBS * 1e9),
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "+".join(knames),
-                "timing": "HIP events around each b64x call on its stream, mean over a second "
-                          "pass of the K steps right after the timed region (events inside it "
-                          "would add ~7 us of GPU idle per event)",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "copy_ceiling_GBps": ceiling[dom]["GBps"] if ceiling else None,
-                "frac_of_copy": achieved / ceiling[dom]["GBps"] if ceiling else None,
-                "frac_of_copy_per_leg": {
-                    "encode": per_launch / (r["enc_ms"] * 1e-3) / 1e9 / ceiling["encode"]["GBps"],
-                    "decode": per_launch / (r["dec_ms"] * 1e-3) / 1e9 / ceiling["decode"]["GBps"],
-                } if ceiling else None,
-                "copy_ceiling": ceiling,
-                # the committed PMC summary is for the 1 GiB workload
-                "traffic": load_traffic(knames) if N == 1 << 30 else None,
-            },
+            "full": full,
+            "dumped_outputs": args.dump_outputs,
+            **per_kernel_figures(r, ceiling, full),
             # the north star's 1 -> 2 -> 4 -> 8 curve: config 4's fixed batch of
             # 1 M buffers, strong-scaled over the ranks (batch_cfg4); `value`
             # above is config 2, one buffer per rank (weak)
@@ -1226,7 +1302,7 @@ def main():
                 "per_rank_kernel_ms": batch["per_rank_kernel_ms"] if batch else None,
                 "exchange_ms": batch["exchange_ms"] if batch else None,
                 "ranks_amortised": batch["ranks_amortised"] if batch else None,
-            },
+            } if full else None,
             "cpu_baseline": cpu,
             "batch_cfg4": batch,
             "batch_cfg3": batch3,

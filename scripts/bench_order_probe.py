@@ -17,7 +17,7 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    sys.argv = [sys.argv[0], "--no-cpu"]
+    sys.argv = [sys.argv[0], "--full", "--no-cpu"]
     import torch
     import bench
     from async_amd import b64

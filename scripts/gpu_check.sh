@@ -19,7 +19,9 @@ step() {  # name, limit, command...
 rocminfo 2>/dev/null | grep -m2 -E "gfx950|Marketing" > gpurun_out/device.txt
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 1200 python -m pytest tests -q -m gpu -k "$K" --timeout 600 -p no:cacheprovider
-step bench 600 python bench.py --steps 20 --warmup 3 "$@"
+step bench 600 python bench.py --full --steps 20 --warmup 3 "$@"
+OUT="${OUT:-$ROOT/bench_out}"  # the profiled bench run's trace goes here
+mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-step rocprof 600 rocprofv3 --kernel-trace --stats -d "$ROOT/gpurun_out/prof" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu
+step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu
 echo ALLDONE

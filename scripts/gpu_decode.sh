@@ -22,8 +22,10 @@ fi
 step dirty 300 python scripts/bench_dirty.py --mib 64 1024 --steps 7
 step dirty_junk 300 python scripts/bench_dirty.py --mib 64 1024 --steps 7 --expect-junk
 step batch_dirty 300 python scripts/bench_batch_dirty.py
-step bench 300 python bench.py --steps 20 --warmup 3 --no-cpu --no-host
+step bench 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --no-host
+OUT="${OUT:-$ROOT/bench_out}"  # the profiled bench run's trace goes here
+mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 step prof_dirty 300 rocprofv3 --kernel-trace --stats -d "$ROOT/gpurun_out/${TAG}_prof_dirty" -o run --output-format csv -- python3 "$ROOT/scripts/bench_dirty.py" --mib 1024 --steps 5
-step prof_bench 300 rocprofv3 --kernel-trace --stats -d "$ROOT/gpurun_out/${TAG}_prof_bench" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu --no-host
+step prof_bench 300 rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_prof_bench" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu --no-host
 echo ALLDONE

@@ -43,7 +43,7 @@ for alias in ("k_encode_flat", "k_decode_pass1", "k_decode_lines", "k_decode_pro
     if cands:
         kernels[alias] = kernels[cands[0]]
 out = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over "
-                 "`bench.py --steps 5 --warmup 1 --no-cpu --no-host --no-mime --batch-steps 3`",
+                 "`bench.py --full --steps 5 --warmup 1 --no-cpu --no-host --no-mime --batch-steps 3`",
        "corrections": "fetch = 2 x FETCH_SIZE KiB (gfx950 half-count), write = WRITE_SIZE KiB",
        "kernels": kernels}
 dst = os.path.join(root, "profiles", f"pmc_{rnd}.json")

@@ -59,6 +59,21 @@ class DecResult(ctypes.Structure):
     ]
 
 
+class Lines(ctypes.Structure):
+    """b64x_lines: line_len characters per line (a multiple of 4), then the
+    first sep_len (1..4) bytes of sep; flags = LINES_TRAILING or 0."""
+
+    _fields_ = [
+        ("line_len", ctypes.c_uint32),
+        ("sep_len", ctypes.c_uint32),
+        ("sep", ctypes.c_uint8 * 4),
+        ("flags", ctypes.c_uint32),
+    ]
+
+
+LINES_TRAILING = 1  # B64X_LINES_TRAILING
+
+assert ctypes.sizeof(Lines) == 16
 assert ctypes.sizeof(DecResult) == 40
 RES_BYTES = ctypes.sizeof(DecResult)  # device buffers for one record
 
@@ -67,6 +82,7 @@ _u32 = ctypes.c_uint32
 _vp = ctypes.c_void_p
 _int = ctypes.c_int
 _ap = ctypes.POINTER(Alphabet)
+_lp = ctypes.POINTER(Lines)
 
 # name -> (restype, argtypes); every symbol include/b64x.h declares.
 SIGNATURES = {
@@ -79,6 +95,9 @@ SIGNATURES = {
                                    ctypes.POINTER(_u32)]),
     "b64x_result_check": (_int, [ctypes.POINTER(DecResult), _u64, ctypes.c_uint, _u32]),
     "b64x_encode_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _ap, _vp]),
+    "b64x_encoded_lines_len": (_u64, [_u64, ctypes.c_bool, _lp]),
+    "b64x_encode_lines_dev": (_int, [_vp, _u64, _vp, _ap, _lp, _vp]),
+    "b64x_encode_lines_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _ap, _lp, _vp]),
     "b64x_decode_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _vp, _ap, _vp]),
     "b64x_encode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _ap, _vp]),
     "b64x_decode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _vp]),
@@ -180,6 +199,17 @@ def load() -> ctypes.CDLL:
 def check(func: str, rc: int) -> None:
     if rc != 0:
         raise B64xError(func, rc)
+
+
+def lines(line_len: int = 76, sep: bytes = b"\r\n", trailing: bool = True) -> Lines:
+    """Build a b64x_lines; the library validates it (-EINVAL)."""
+    sep = bytes(sep)
+    if not 1 <= len(sep) <= 4:
+        raise ValueError("the separator is 1 to 4 bytes")
+    if not 0 <= line_len < 1 << 32:
+        raise ValueError("line_len out of range")
+    return Lines(line_len, len(sep), (ctypes.c_uint8 * 4)(*sep),
+                 LINES_TRAILING if trailing else 0)
 
 
 def alphabet(pos62=-1, pos63=-1, pad=True, padchar=-1) -> Alphabet:

@@ -8,7 +8,10 @@ buffers and batches instead of a pull-model stream:
 
     encode(x)                  one buffer      (b64x_encode_dev)
     decode(x)                  one buffer      (b64x_decode_dev)
+    encode_lines(x)            one buffer, line-wrapped text: MIME 76/CRLF,
+                               PEM 64/LF      (b64x_encode_lines_dev)
     encode_strided / decode_strided            uniform batches
+    encode_lines_strided                       uniform batches, each row wrapped
     encode_batch / decode_batch                ragged batches (offsets)
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
@@ -82,6 +85,38 @@ def encode(x: torch.Tensor, out: torch.Tensor | None = None, abc=None,
         raise ValueError("output too small")
     _lib.check("b64x_encode_dev", lib.b64x_encode_dev(
         _ptr(x), n, _ptr(out), ctypes.byref(a), _stream(stream)))
+    return out[:m]
+
+
+def encoded_lines_len(n: int, line_len: int = 76, sep: bytes = b"\r\n",
+                      trailing: bool = True, pad: bool = True) -> int:
+    """Bytes encode_lines() writes for n input bytes."""
+    fmt = _lib.lines(line_len, sep, trailing)
+    if line_len <= 0 or line_len % 4:
+        raise ValueError("line_len must be a positive multiple of 4")
+    return int(_lib.load().b64x_encoded_lines_len(n, pad, ctypes.byref(fmt)))
+
+
+def encode_lines(x: torch.Tensor, line_len: int = 76, sep: bytes = b"\r\n",
+                 trailing: bool = True, out: torch.Tensor | None = None, abc=None,
+                 stream=None) -> torch.Tensor:
+    """Base64-encode a device buffer as line-wrapped text: lines of line_len
+    characters, `sep` after each (after the last one only with `trailing`).
+    The defaults are RFC 2045 (MIME); 64, b"\\n" is a PEM body; 76, b"\\n" is
+    base64.encodebytes.  Returns the text tensor."""
+    lib = _lib.load()
+    a = _abc(abc)
+    _u8(x, "input")
+    n = x.numel()
+    m = encoded_lines_len(n, line_len, sep, trailing, a.pad)
+    fmt = _lib.lines(line_len, sep, trailing)
+    if out is None:
+        out = torch.empty(max(m, 1), dtype=torch.uint8, device=x.device)
+    _u8(out, "output")
+    if out.numel() < m:
+        raise ValueError("output too small")
+    _lib.check("b64x_encode_lines_dev", lib.b64x_encode_lines_dev(
+        _ptr(x), n, _ptr(out), ctypes.byref(a), ctypes.byref(fmt), _stream(stream)))
     return out[:m]
 
 
@@ -162,6 +197,26 @@ def encode_strided(x: torch.Tensor, in_stride: int, length: int, nbuf: int,
     _lib.check("b64x_encode_strided", lib.b64x_encode_strided(
         _ptr(x), in_stride, length, nbuf, _ptr(out), out_stride, ctypes.byref(a),
         _stream(stream)))
+
+
+def encode_lines_strided(x: torch.Tensor, in_stride: int, length: int, nbuf: int,
+                         out: torch.Tensor, out_stride: int, line_len: int = 76,
+                         sep: bytes = b"\r\n", trailing: bool = True, abc=None,
+                         stream=None) -> None:
+    """Row i (`length` bytes at x + i*in_stride) wrapped on its own into
+    out + i*out_stride; every row gets encoded_lines_len(length, ...) bytes."""
+    lib = _lib.load()
+    a = _abc(abc)
+    _u8(x, "input")
+    _u8(out, "output")
+    m = encoded_lines_len(length, line_len, sep, trailing, a.pad)
+    fmt = _lib.lines(line_len, sep, trailing)
+    if nbuf and (x.numel() < (nbuf - 1) * in_stride + length or
+                 out.numel() < (nbuf - 1) * out_stride + m):
+        raise ValueError("buffers too small for the batch")
+    _lib.check("b64x_encode_lines_strided", lib.b64x_encode_lines_strided(
+        _ptr(x), in_stride, length, nbuf, _ptr(out), out_stride, ctypes.byref(a),
+        ctypes.byref(fmt), _stream(stream)))
 
 
 def decode_strided(x: torch.Tensor, in_stride: int, length: int, nbuf: int,

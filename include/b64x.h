@@ -88,7 +88,7 @@
 extern "C" {
 #endif
 
-#define B64X_ABI_VERSION 4
+#define B64X_ABI_VERSION 5
 
 /* Alphabet descriptor.  (char) -1 selects the reference's defaults,
  * exactly like base64_encode()/base64_decode() (ref
@@ -223,6 +223,52 @@ int b64x_decode_batch(const void *d_in, const uint64_t *d_in_off,
                       uint32_t nbuf, void *d_out, const uint64_t *d_out_off,
                       uint64_t *d_outlen, const b64x_alphabet *abc,
                       void *stream);
+
+/* ---- line-wrapped encode (MIME 76/CRLF, PEM 64/LF) --------------------- */
+
+/* The shape of line-wrapped base64 text: lines of line_len characters, each
+ * followed by the separator.  line_len must be a multiple of 4 (>= 4), so
+ * that line k is the plain encoding of input bytes [3k*line_len/4,
+ * 3(k+1)*line_len/4) and every line starts on a 3-byte group. */
+typedef struct b64x_lines {
+    uint32_t line_len;   /* L: alphabet/pad characters per line; a multiple of 4, >= 4 */
+    uint32_t sep_len;    /* s: 1..4 */
+    uint8_t  sep[4];     /* the separator bytes; the first sep_len are used */
+    uint32_t flags;      /* B64X_LINES_TRAILING */
+} b64x_lines;
+#define B64X_LINES_TRAILING 1u  /* also write the separator after the last line */
+
+/* Bytes b64x_encode_lines_dev() writes for n input bytes: with E =
+ * b64x_encoded_len(n, pad), E + s*(ceil(E/L) - (trailing ? 0 : 1)) for
+ * E > 0, and 0 for E == 0 (or an invalid fmt). */
+uint64_t b64x_encoded_lines_len(uint64_t n, bool pad, const b64x_lines *fmt);
+
+/* Encode n bytes at d_in as line-wrapped text at d_out: the characters
+ * b64x_encode_dev() writes for the same input and alphabet, cut into
+ * ceil(E/L) lines of L characters (the last may be shorter), the separator
+ * after every line but the last and, with B64X_LINES_TRAILING, after the
+ * last one too; nothing for n == 0.  Exact: no model, no hint.
+ * L = 76, "\n", trailing is Python's base64.encodebytes; L = 76, "\r\n" is
+ * RFC 2045; L = 64, "\n", trailing is a PEM body.
+ * -EINVAL: fmt NULL, L == 0 or not a multiple of 4, s outside 1..4, unknown
+ * flag bits, or a separator byte that is an alphabet character under abc
+ * (the 62 alphanumerics and the effective pos62/pos63: the text would not
+ * decode back).  Checked in this order: n == 0 returns 0, NULL buffers
+ * -EINVAL, the format, then -ENODEV without a gfx950 device (no CPU path).
+ * Input and output must not overlap.  Any alignment is accepted; 4-byte
+ * aligned d_in with 16-byte aligned d_out is the fast path.  No 32-bit limit
+ * on n.  The launch is asynchronous and capture-safe: the format travels as
+ * kernel arguments, nothing is allocated or synchronised. */
+int b64x_encode_lines_dev(const void *d_in, uint64_t n, void *d_out,
+                          const b64x_alphabet *abc, const b64x_lines *fmt, void *stream);
+
+/* nbuf rows of `len` bytes at d_in + i*in_stride, each wrapped on its own
+ * into d_out + i*out_stride; every row gets b64x_encoded_lines_len(len, pad,
+ * fmt) bytes.  -EINVAL also for out_stride below that length or in_stride <
+ * len.  Rows at 4-byte aligned addresses (both sides) are the fast shape. */
+int b64x_encode_lines_strided(const void *d_in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                              void *d_out, uint64_t out_stride,
+                              const b64x_alphabet *abc, const b64x_lines *fmt, void *stream);
 
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 

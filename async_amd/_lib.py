@@ -73,8 +73,27 @@ class Lines(ctypes.Structure):
 
 LINES_TRAILING = 1  # B64X_LINES_TRAILING
 
+
+class StrictResult(ctypes.Structure):
+    """b64x_strict_result, 24 bytes, written by the device: the bytes decoded,
+    or the kind (STRICT_*) and text offset of the first offence."""
+
+    _fields_ = [
+        ("out_len", ctypes.c_uint64),
+        ("err_pos", ctypes.c_uint64),
+        ("err", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+# B64X_STRICT_*
+STRICT_OK, STRICT_CHAR, STRICT_SEP, STRICT_PAD, STRICT_BITS, STRICT_LENGTH = range(6)
+STRICT_NAMES = ("ok", "char", "sep", "pad", "bits", "length")
+
 assert ctypes.sizeof(Lines) == 16
 assert ctypes.sizeof(DecResult) == 40
+assert ctypes.sizeof(StrictResult) == 24
+STRICT_RES_BYTES = ctypes.sizeof(StrictResult)
 RES_BYTES = ctypes.sizeof(DecResult)  # device buffers for one record
 
 _u64 = ctypes.c_uint64
@@ -98,6 +117,9 @@ SIGNATURES = {
     "b64x_encoded_lines_len": (_u64, [_u64, ctypes.c_bool, _lp]),
     "b64x_encode_lines_dev": (_int, [_vp, _u64, _vp, _ap, _lp, _vp]),
     "b64x_encode_lines_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _ap, _lp, _vp]),
+    "b64x_strict_decoded_cap": (_u64, [_u64, _lp]),
+    "b64x_decode_strict_dev": (_int, [_vp, _u64, _vp, _vp, _ap, _lp, _vp]),
+    "b64x_decode_strict_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _vp, _ap, _lp, _vp]),
     "b64x_decode_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _vp, _ap, _vp]),
     "b64x_encode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _ap, _vp]),
     "b64x_decode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _vp]),

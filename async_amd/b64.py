@@ -10,7 +10,12 @@ buffers and batches instead of a pull-model stream:
     decode(x)                  one buffer      (b64x_decode_dev)
     encode_lines(x)            one buffer, line-wrapped text: MIME 76/CRLF,
                                PEM 64/LF      (b64x_encode_lines_dev)
+    decode_strict(x)           one buffer, strict: accepts exactly what
+                               encode / encode_lines write, else the kind and
+                               offset of the first offence
+                                              (b64x_decode_strict_dev)
     encode_strided / decode_strided            uniform batches
+    decode_strict_strided                      uniform batches, strict
     encode_lines_strided                       uniform batches, each row wrapped
     encode_batch / decode_batch                ragged batches (offsets)
 
@@ -25,7 +30,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import RES_BYTES, B64xError, DecResult, alphabet  # noqa: F401
+from ._lib import (RES_BYTES, STRICT_RES_BYTES, B64xError, DecResult,  # noqa: F401
+                   StrictResult, alphabet)
 
 HOLD_TAIL = 1  # B64X_DEC_HOLD_TAIL
 EXPECT_JUNK = 2  # B64X_DEC_EXPECT_JUNK
@@ -183,6 +189,110 @@ def decode(x: torch.Tensor, out: torch.Tensor | None = None, abc=None,
         _ptr(workspace) if workspace is not None else None, s.cuda_stream,
         ctypes.byref(seq)))
     return Decoded(out, result, n, flags & HOLD_TAIL, seq.value, s)
+
+
+class B64xFormatError(ValueError):
+    """A strict decode refused its text: `kind` is the B64X_STRICT_* code of
+    the first offence and `pos` its byte offset in the text."""
+
+    def __init__(self, kind: int, pos: int):
+        self.kind = kind
+        self.pos = pos
+        name = _lib.STRICT_NAMES[kind] if 0 <= kind < len(_lib.STRICT_NAMES) else str(kind)
+        super().__init__(f"not canonical base64: {name} at offset {pos}")
+
+
+def _fmt(line_len, sep, trailing):
+    """(b64x_lines or None, a byref of it or None) for line_len (None: plain)."""
+    if line_len is None:
+        return None, None
+    fmt = _lib.lines(line_len, sep, trailing)
+    return fmt, ctypes.byref(fmt)
+
+
+def strict_decoded_cap(nchars: int, line_len: int | None = None, sep: bytes = b"\r\n",
+                       trailing: bool = True) -> int:
+    """Output capacity decode_strict() needs for nchars bytes of text."""
+    _, ref = _fmt(line_len, sep, trailing)
+    return int(_lib.load().b64x_strict_decoded_cap(nchars, ref))
+
+
+@dataclass
+class StrictDecoded:
+    out: torch.Tensor          # capacity-sized output buffer
+    result: torch.Tensor       # b64x_strict_result (STRICT_RES_BYTES) on the device
+    stream: object = None      # the stream the decode ran on
+
+    def info(self) -> StrictResult:
+        """The call's record: waits for the decode's own stream and copies
+        the record back."""
+        s = self.stream if self.stream is not None else torch.cuda.current_stream()
+        s.synchronize()
+        host = self.result[:STRICT_RES_BYTES].cpu().numpy()
+        return StrictResult.from_buffer_copy(host.tobytes())
+
+    def bytes(self) -> torch.Tensor:
+        """The decoded bytes, or B64xFormatError with the first offence."""
+        r = self.info()
+        if r.err:
+            raise B64xFormatError(r.err, r.err_pos)
+        return self.out[: r.out_len]
+
+
+def decode_strict(x: torch.Tensor, line_len: int | None = None, sep: bytes = b"\r\n",
+                  trailing: bool = True, out: torch.Tensor | None = None, abc=None,
+                  result: torch.Tensor | None = None, stream=None) -> StrictDecoded:
+    """Strictly decode a device buffer of base64 text: plain (line_len None,
+    what encode() writes) or line-wrapped (what encode_lines() writes for the
+    same line_len, sep and trailing).  Any other text is refused: the record
+    (StrictDecoded.info()) names the kind and offset of the first offence."""
+    lib = _lib.load()
+    a = _abc(abc)
+    _u8(x, "input")
+    n = x.numel()
+    fmt, ref = _fmt(line_len, sep, trailing)
+    cap = int(lib.b64x_strict_decoded_cap(n, ref))
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=x.device)
+    _u8(out, "output")
+    if out.numel() < cap:
+        raise ValueError("output too small")
+    if result is None:
+        result = torch.empty(STRICT_RES_BYTES, dtype=torch.uint8, device=x.device)
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES:
+        raise ValueError("result too small")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    # an empty tensor has no address; nothing is read through the stand-in
+    _lib.check("b64x_decode_strict_dev", lib.b64x_decode_strict_dev(
+        _ptr(x) if n else _ptr(result), n, _ptr(out) if out.numel() else _ptr(result),
+        _ptr(result), ctypes.byref(a), ref, s.cuda_stream))
+    return StrictDecoded(out, result, s)
+
+
+def decode_strict_strided(x: torch.Tensor, in_stride: int, length: int, nbuf: int,
+                          out: torch.Tensor, out_stride: int, result: torch.Tensor,
+                          line_len: int | None = None, sep: bytes = b"\r\n",
+                          trailing: bool = True, abc=None, stream=None) -> None:
+    """Row i (`length` bytes of text at x + i*in_stride) strictly decoded on
+    its own into out + i*out_stride; its b64x_strict_result goes to bytes
+    [24 i, 24 i + 24) of `result` (a uint8 tensor of 24*nbuf bytes)."""
+    lib = _lib.load()
+    a = _abc(abc)
+    _u8(x, "input")
+    _u8(out, "output")
+    _u8(result, "result")
+    fmt, ref = _fmt(line_len, sep, trailing)
+    cap = int(lib.b64x_strict_decoded_cap(length, ref))
+    if result.numel() < STRICT_RES_BYTES * nbuf:
+        raise ValueError("result must hold 24 bytes per row")
+    if nbuf and (x.numel() < (nbuf - 1) * in_stride + length or
+                 out.numel() < (nbuf - 1) * out_stride + cap):
+        raise ValueError("buffers too small for the batch")
+    _lib.check("b64x_decode_strict_strided", lib.b64x_decode_strict_strided(
+        _ptr(x) if x.numel() else _ptr(result), in_stride, length, nbuf,
+        _ptr(out) if out.numel() else _ptr(result), out_stride, _ptr(result),
+        ctypes.byref(a), ref, _stream(stream)))
 
 
 def encode_strided(x: torch.Tensor, in_stride: int, length: int, nbuf: int,

@@ -88,12 +88,13 @@
 extern "C" {
 #endif
 
-#define B64X_ABI_VERSION 5
+#define B64X_ABI_VERSION 6
 
 /* Alphabet descriptor.  (char) -1 selects the reference's defaults,
  * exactly like base64_encode()/base64_decode() (ref
  * src/base64encoder.c:40-43, src/base64decoder.c:31-32).  `pad` and
- * `padchar` are ignored by the decoder, which has no pad parameter. */
+ * `padchar` are ignored by the lenient decoder, which has no pad parameter
+ * (b64x_decode_strict_* honour them). */
 typedef struct b64x_alphabet {
     char pos62;
     char pos63;
@@ -269,6 +270,85 @@ int b64x_encode_lines_dev(const void *d_in, uint64_t n, void *d_out,
 int b64x_encode_lines_strided(const void *d_in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
                               void *d_out, uint64_t out_stride,
                               const b64x_alphabet *abc, const b64x_lines *fmt, void *stream);
+
+/* ---- strict decode with first-error position --------------------------- */
+
+/* b64x_decode_strict_* accept exactly the texts the encoders above write
+ * under the same alphabet and line format -- strict(t) accepts <=> t ==
+ * encode[_lines](decode(t)) -- decode them, and otherwise report the kind and
+ * the byte offset of the first offence.  Unlike the lenient decoder they read
+ * `abc` as the encoder does: (char) -1 gives the defaults, and `pad` /
+ * `padchar` are honoured.
+ *
+ * The result is, for any input, what this scalar procedure returns:
+ *  1. Length, from nchars, fmt and pad alone.  Plain: E = nchars.  Wrapped
+ *     (P = L + s): m = nchars (trailing) or nchars + s, (k, r) = divmod(m, P);
+ *     r == 0: E = kL; r > s: E = kL + r - s; 0 < r <= s: no E; nchars == 0:
+ *     E = 0.  There is no valid E either if b64x_encoded_lines_len's formula
+ *     for E does not give nchars back, if pad and E mod 4 != 0, or if not pad
+ *     and E mod 4 == 1.  No E: {LENGTH, err_pos = nchars}, nothing is read.
+ *  2. Positions.  Character e stands at offset e (plain) or floor(e/L) P +
+ *     e mod L.  The separator follows every line, a short last one included;
+ *     it follows the very last line only with B64X_LINES_TRAILING.
+ *  3. Pads.  With pad, npad = 0 unless character E-1 is the pad character;
+ *     then 2 if character E-2 is too, else 1.  Without pad, 0.  D = E - npad.
+ *  4. Offences.  A separator byte != sep[j] is SEP.  A character e < D that
+ *     is the pad character (with pad) is PAD, else one outside the 64 is
+ *     CHAR.  Character D-1, with D mod 4 in {2, 3}, whose sextet has any of
+ *     its low 4 / 2 bits set is BITS.  A byte has at most one kind; the
+ *     record holds the kind and offset of the offence at the lowest offset,
+ *     however many there are.
+ *  5. No offence: out_len = 3 floor(D/4) + (0, -, 1, 2)[D mod 4], and the
+ *     bytes are those of the D sextets. */
+#define B64X_STRICT_OK      0u
+#define B64X_STRICT_CHAR    1u  /* a byte at a character position that is neither in the alphabet nor the pad character */
+#define B64X_STRICT_SEP     2u  /* a byte at a separator position that is not that separator byte */
+#define B64X_STRICT_PAD     3u  /* the pad character where no pad may stand */
+#define B64X_STRICT_BITS    4u  /* the last data character carries nonzero unused low bits */
+#define B64X_STRICT_LENGTH  5u  /* no encoder output has this length; err_pos == nchars */
+
+typedef struct b64x_strict_result {
+    uint64_t out_len;   /* bytes decoded; 0 when err != 0 */
+    uint64_t err_pos;   /* offset in the text of the first offence; 0 when err == 0 */
+    uint32_t err;       /* B64X_STRICT_* */
+    uint32_t reserved;  /* 0 */
+} b64x_strict_result;
+
+/* Output capacity of a strict decode of nchars bytes of text: 3*ceil(E/4)
+ * for the E characters a text of that length holds (step 1 without the pad
+ * rules; a length no text has counts the characters of its whole lines).
+ * fmt NULL: plain.  Never more than b64x_decoded_cap(nchars); 0 for a fmt
+ * with line_len == 0 or sep_len outside 1..4. */
+uint64_t b64x_strict_decoded_cap(uint64_t nchars, const b64x_lines *fmt);
+
+/* Strictly decode the nchars bytes at d_in (fmt NULL: plain text) into d_out
+ * (capacity b64x_strict_decoded_cap(nchars, fmt)); *d_res (device memory,
+ * 8-byte aligned) receives the record.  The call writes the whole record
+ * itself (the caller need not zero it), nothing outside [d_out, d_out + cap)
+ * and the record, and reads nothing outside [d_in, d_in + nchars).  With
+ * err != 0 the output bytes are unspecified.  nchars == 0 is a valid text
+ * (out_len 0) and still writes its record.
+ * -EINVAL: a NULL buffer or record (or a record not 8-byte aligned); a fmt
+ * b64x_encode_lines_dev would refuse (the same rules in the same order);
+ * pos62 == pos63; an alphanumeric pos62 or pos63; pad set and padchar one of
+ * the 64 alphabet characters.  Then -ENODEV without a gfx950 device.
+ * Asynchronous, capture-safe and exact: no allocation, no synchronisation, no
+ * workspace, no library state, no hint (a memset node, the decode kernel and
+ * a one-thread-per-row kernel that gives the record its final form).  Any
+ * alignment is accepted; 4-byte aligned d_in and d_out with L >= 16 is the
+ * fast path.  No 32-bit limit on nchars. */
+int b64x_decode_strict_dev(const void *d_in, uint64_t nchars, void *d_out,
+                           b64x_strict_result *d_res, const b64x_alphabet *abc,
+                           const b64x_lines *fmt /* NULL: plain */, void *stream);
+
+/* nbuf rows of `len` bytes of text at d_in + i*in_stride, each decoded on its
+ * own into d_out + i*out_stride, its record in d_res[i] (err_pos is an offset
+ * in the row).  -EINVAL also for in_stride < len or out_stride below
+ * b64x_strict_decoded_cap(len, fmt).  Rows at 4-byte aligned addresses (both
+ * sides) are the fast shape. */
+int b64x_decode_strict_strided(const void *d_in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                               void *d_out, uint64_t out_stride, b64x_strict_result *d_res /* nbuf */,
+                               const b64x_alphabet *abc, const b64x_lines *fmt, void *stream);
 
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 

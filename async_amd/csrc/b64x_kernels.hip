@@ -3830,6 +3830,10 @@ DEV uint64_t decode_buf_bits(const P2dSmem &sm, uint4 *bq, const uint8_t *src, u
         }
         // flush the whole dwords; the partial one becomes dword 1
         const uint32_t kcut = (pb >> 3) & ~3u;
+        // An unaligned dst (lo > 4) and so few characters so far (junk) that
+        // the window ends inside dword 1, before dst's first byte: nothing to
+        // flush yet, and moving the window (lo = 4) would put it below dst.
+        if (kcut < lo) continue;
         store_bits(bits, lo, kcut, dst + done - lo);
         done += kcut - lo;
         const uint32_t keep = bits[kcut >> 2];

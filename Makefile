@@ -39,6 +39,10 @@ OBJDIR   = build
 KERNEL_SRC = async_amd/csrc/b64x_kernels.hip
 WRAP_SRC   = async_amd/csrc/b64x_wrap.hip
 STRICT_SRC = async_amd/csrc/b64x_strict.hip
+BATCH_SRC  = async_amd/csrc/b64x_lines_batch.hip
+# The per-lane bodies the one-buffer and the ragged-batch units share.
+WRAP_BODY   = async_amd/csrc/b64x_wrap_body.h async_amd/csrc/b64x_block_sync.h
+STRICT_BODY = async_amd/csrc/b64x_strict_body.h async_amd/csrc/b64x_block_sync.h
 HOST_SRC   = async_amd/csrc/fsalloc.c async_amd/csrc/loop.c async_amd/csrc/streams.c \
              async_amd/csrc/framing.c async_amd/csrc/fdstreams.c async_amd/csrc/b64_hub.c \
              async_amd/csrc/b64_stages.c async_amd/csrc/b64_pin.c
@@ -63,11 +67,15 @@ $(OBJDIR)/b64x_kernels.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_ch
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The line-wrapped encode: a code object of its own, linked after the kernels'.
-$(OBJDIR)/b64x_wrap.o: $(WRAP_SRC) $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_wrap.o: $(WRAP_SRC) $(WRAP_BODY) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The strict decode: likewise, linked after both.
-$(OBJDIR)/b64x_strict.o: $(STRICT_SRC) $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_strict.o: $(STRICT_SRC) $(STRICT_BODY) $(HEADERS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# Their ragged-batch forms: likewise, linked after all three.
+$(OBJDIR)/b64x_lines_batch.o: $(BATCH_SRC) $(WRAP_BODY) $(STRICT_BODY) async_amd/csrc/b64x_lines_plan.h $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)
@@ -76,13 +84,13 @@ $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/
 $(OBJDIR)/b64x_kernels_hooks.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_check.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DB64X_TEST_HOOKS -c $< -o $@
 
-$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o
+$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libb64x_hooks.so
 
-$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(HOST_OBJ)
+$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64.so
 
-$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
+$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64_core.so
 
 $(ORACLE): oracle/b64_oracle.c oracle/b64_oracle.h

@@ -123,6 +123,8 @@ SIGNATURES = {
     "b64x_decode_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _vp, _ap, _vp]),
     "b64x_encode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _ap, _vp]),
     "b64x_decode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _vp]),
+    "b64x_encode_lines_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _ap, _lp, _vp]),
+    "b64x_decode_strict_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _lp, _vp]),
     "b64x_session_open": (_vp, [_u64]),
     "b64x_session_close": (None, [_vp]),
     "b64x_session_acquire": (_vp, [_u64]),

@@ -18,6 +18,12 @@ buffers and batches instead of a pull-model stream:
     decode_strict_strided                      uniform batches, strict
     encode_lines_strided                       uniform batches, each row wrapped
     encode_batch / decode_batch                ragged batches (offsets)
+    encode_lines_batch                         ragged batches, each buffer wrapped
+                                              (b64x_encode_lines_batch)
+    decode_strict_batch                        ragged batches, strict, one record
+                               per buffer     (b64x_decode_strict_batch)
+    lines_batch_layout / strict_batch_layout   their output offsets, from the
+                               input offsets, on the tensor's own device
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
 missing or a call fails; nothing here computes base64 on the CPU.
@@ -377,6 +383,107 @@ def decode_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,
     _lib.check("b64x_decode_batch", lib.b64x_decode_batch(
         _ptr(_u8(x, "input")), _ptr(in_off), nbuf, _ptr(_u8(out, "output")),
         _ptr(out_off), _ptr(outlen), ctypes.byref(a), _stream(stream)))
+
+
+def _lengths(in_off: torch.Tensor) -> torch.Tensor:
+    if in_off.dtype != torch.int64 or in_off.dim() != 1 or in_off.numel() < 1:
+        raise ValueError("in_off must be a 1-D int64 tensor of nbuf + 1 entries")
+    return in_off[1:] - in_off[:-1]
+
+
+def _starts(sizes: torch.Tensor, align: int) -> torch.Tensor:
+    """nbuf + 1 offsets of buffers of `sizes` bytes laid out in order, every
+    start rounded up to `align`; the last entry is the arena's size."""
+    if align < 1:
+        raise ValueError("align must be at least 1")
+    out = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=sizes.device)
+    torch.cumsum((sizes + (align - 1)) // align * align, 0, out=out[1:])
+    return out
+
+
+def lines_batch_layout(in_off: torch.Tensor, line_len: int = 76, sep: bytes = b"\r\n",
+                       trailing: bool = True, pad: bool = True, align: int = 1) -> torch.Tensor:
+    """Output offsets for encode_lines_batch(): nbuf + 1 int64 entries, entry
+    i the start of buffer i's wrapped text (rounded up to `align`), the last
+    the size of the arena.  Computed from in_off on its own device with
+    integer tensor ops: no host synchronisation (a CPU tensor works too)."""
+    s = len(bytes(sep))
+    if line_len <= 0 or line_len % 4 or not 1 <= s <= 4:
+        raise ValueError("line_len must be a positive multiple of 4, the separator 1 to 4 bytes")
+    n = _lengths(in_off)
+    chars = (n + 2) // 3 * 4 if pad else (4 * n + 2) // 3
+    lines = (chars + (line_len - 1)) // line_len
+    text = chars + s * (lines - (0 if trailing else 1))
+    return _starts(torch.where(chars > 0, text, torch.zeros_like(text)), align)
+
+
+def strict_batch_layout(in_off: torch.Tensor, line_len: int | None = None,
+                        sep: bytes = b"\r\n", trailing: bool = True,
+                        align: int = 1) -> torch.Tensor:
+    """Output offsets for decode_strict_batch(): nbuf + 1 int64 entries, entry
+    i the start of text i's decode capacity (strict_decoded_cap of its length,
+    the start rounded up to `align`), the last the size of the arena.  Like
+    lines_batch_layout(), tensor ops on in_off's own device."""
+    n = _lengths(in_off)
+    if line_len is None:
+        chars = n
+    else:
+        s = len(bytes(sep))
+        if line_len <= 0 or not 1 <= s <= 4:
+            raise ValueError("line_len must be positive, the separator 1 to 4 bytes")
+        pitch = line_len + s
+        m = n if trailing else n + s
+        k = m // pitch
+        chars = k * line_len + torch.clamp(m - k * pitch - s, min=0)
+    return _starts((chars + 3) // 4 * 3, align)
+
+
+def encode_lines_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,
+                       out_off: torch.Tensor, line_len: int = 76, sep: bytes = b"\r\n",
+                       trailing: bool = True, abc=None, stream=None) -> None:
+    """Ragged batch of encode_lines(): buffer i = x[in_off[i]:in_off[i+1]] is
+    wrapped on its own into out[out_off[i]:] (lines_batch_layout() gives the
+    offsets).  The lengths are read on the device: a call captured into a
+    graph replays on other lengths written into the same offset tensors."""
+    lib = _lib.load()
+    a = _abc(abc)
+    nbuf = in_off.numel() - 1
+    _offsets(in_off, nbuf + 1, "in_off")
+    _offsets(out_off, nbuf, "out_off")
+    fmt = _lib.lines(line_len, sep, trailing)
+    # an empty tensor has no address; nothing is read through the stand-in
+    _u8(x, "input")
+    _u8(out, "output")
+    _lib.check("b64x_encode_lines_batch", lib.b64x_encode_lines_batch(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf,
+        _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), ctypes.byref(a),
+        ctypes.byref(fmt), _stream(stream)))
+
+
+def decode_strict_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,
+                        out_off: torch.Tensor, result: torch.Tensor,
+                        line_len: int | None = None, sep: bytes = b"\r\n",
+                        trailing: bool = True, abc=None, stream=None) -> None:
+    """Ragged batch of decode_strict(): text i = x[in_off[i]:in_off[i+1]] is
+    strictly decoded on its own into out[out_off[i]:] (strict_batch_layout()
+    gives the offsets); its b64x_strict_result goes to bytes [24 i, 24 i + 24)
+    of `result` (a uint8 tensor of 24*nbuf bytes), err_pos an offset in text
+    i.  Replays on other lengths like encode_lines_batch()."""
+    lib = _lib.load()
+    a = _abc(abc)
+    nbuf = in_off.numel() - 1
+    _offsets(in_off, nbuf + 1, "in_off")
+    _offsets(out_off, nbuf, "out_off")
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES * nbuf:
+        raise ValueError("result must hold 24 bytes per buffer")
+    fmt, ref = _fmt(line_len, sep, trailing)
+    _u8(x, "input")
+    _u8(out, "output")
+    _lib.check("b64x_decode_strict_batch", lib.b64x_decode_strict_batch(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf,
+        _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), _ptr(result),
+        ctypes.byref(a), ref, _stream(stream)))
 
 
 def release_stream(stream=None) -> None:

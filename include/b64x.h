@@ -88,7 +88,7 @@
 extern "C" {
 #endif
 
-#define B64X_ABI_VERSION 6
+#define B64X_ABI_VERSION 7
 
 /* Alphabet descriptor.  (char) -1 selects the reference's defaults,
  * exactly like base64_encode()/base64_decode() (ref
@@ -349,6 +349,55 @@ int b64x_decode_strict_dev(const void *d_in, uint64_t nchars, void *d_out,
 int b64x_decode_strict_strided(const void *d_in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
                                void *d_out, uint64_t out_stride, b64x_strict_result *d_res /* nbuf */,
                                const b64x_alphabet *abc, const b64x_lines *fmt, void *stream);
+
+/* ---- ragged batches of the two calls above ----------------------------- */
+
+/* Both calls address their buffers as b64x_encode_batch does: buffer i is
+ * d_in[d_in_off[i] .. d_in_off[i+1]) (nbuf + 1 monotone offsets, device
+ * memory) and its output starts at d_out + d_out_off[i] (nbuf entries).  The
+ * lengths are read on the device when the kernel runs: the grid and every
+ * kernel argument depend on nbuf, abc and fmt only, so a call captured into a
+ * graph can be replayed on batches of other lengths by rewriting the offset
+ * arrays (the one-buffer and strided calls bake the length into their kernel
+ * arguments).  Asynchronous, exact and capture-safe: no allocation, no
+ * synchronisation, no workspace, no library state, no hint.
+ * Any alignment of any buffer is accepted, mixed within one batch; a buffer
+ * whose input and output addresses are both 4-byte aligned takes the fast
+ * path (with L >= 16), the others are written bytewise.  No 32-bit limit on a
+ * buffer's length -- but one wave walks one buffer, so a buffer of hundreds
+ * of MiB, exact as it is, runs at one wave's rate (the kernels balance a
+ * batch over buffers, not over the bytes of one): such a buffer belongs on
+ * the one-buffer calls, as with b64x_encode_batch's one block per buffer. */
+
+/* Buffer i wrapped on its own: byte for byte what b64x_encode_lines_dev()
+ * writes for it under the same abc and fmt, b64x_encoded_lines_len(len_i,
+ * pad, fmt) bytes; nothing for an empty buffer.  Nothing is written outside
+ * those ranges, and nothing outside buffer i is read for its text.
+ * Checked in this order: nbuf == 0 returns 0, NULL pointers -EINVAL, the
+ * format rules of b64x_encode_lines_dev (fmt NULL is -EINVAL here: plain is
+ * b64x_encode_batch), then -ENODEV. */
+int b64x_encode_lines_batch(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
+                            void *d_out, const uint64_t *d_out_off,
+                            const b64x_alphabet *abc, const b64x_lines *fmt, void *stream);
+
+/* Text i strictly decoded on its own into d_out + d_out_off[i] (capacity
+ * b64x_strict_decoded_cap(len_i, fmt)); d_res[i] is exactly the record the
+ * scalar procedure above gives for text i alone, err_pos an offset inside the
+ * buffer: {LENGTH, err_pos = len_i} where no encoder output has that length
+ * (decided per buffer, on the device), {0, 0, OK} for an empty text.  The
+ * call writes every record whole (the caller need not zero them), nothing
+ * outside [d_out_off[i], d_out_off[i] + cap_i) and the records, and reads
+ * nothing outside buffer i.  One kernel: a wave owns its buffer alone and
+ * keeps the lowest offence to itself, so there is no memset node, no global
+ * atomic and no record kernel.
+ * Checked in this order: nbuf == 0 returns 0, NULL pointers (or a record array
+ * not 8-byte aligned) -EINVAL, the format and alphabet rules of
+ * b64x_decode_strict_dev, then -ENODEV. */
+int b64x_decode_strict_batch(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
+                             void *d_out, const uint64_t *d_out_off,
+                             b64x_strict_result *d_res /* nbuf */,
+                             const b64x_alphabet *abc, const b64x_lines *fmt /* NULL: plain */,
+                             void *stream);
 
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 

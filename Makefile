@@ -40,9 +40,11 @@ KERNEL_SRC = async_amd/csrc/b64x_kernels.hip
 WRAP_SRC   = async_amd/csrc/b64x_wrap.hip
 STRICT_SRC = async_amd/csrc/b64x_strict.hip
 BATCH_SRC  = async_amd/csrc/b64x_lines_batch.hip
-# The per-lane bodies the one-buffer and the ragged-batch units share.
-WRAP_BODY   = async_amd/csrc/b64x_wrap_body.h async_amd/csrc/b64x_block_sync.h
-STRICT_BODY = async_amd/csrc/b64x_strict_body.h async_amd/csrc/b64x_block_sync.h
+# Every header the line-wrapped encode, the strict decode and their ragged
+# forms include: the plan arithmetic, the common device header and the
+# per-lane bodies the one-buffer and the ragged-batch units share.
+LINES_HDRS = async_amd/csrc/b64x_lines_plan.h async_amd/csrc/b64x_lines_dev.h \
+             async_amd/csrc/b64x_wrap_body.h async_amd/csrc/b64x_strict_body.h
 HOST_SRC   = async_amd/csrc/fsalloc.c async_amd/csrc/loop.c async_amd/csrc/streams.c \
              async_amd/csrc/framing.c async_amd/csrc/fdstreams.c async_amd/csrc/b64_hub.c \
              async_amd/csrc/b64_stages.c async_amd/csrc/b64_pin.c
@@ -67,15 +69,15 @@ $(OBJDIR)/b64x_kernels.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_ch
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The line-wrapped encode: a code object of its own, linked after the kernels'.
-$(OBJDIR)/b64x_wrap.o: $(WRAP_SRC) $(WRAP_BODY) $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_wrap.o: $(WRAP_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The strict decode: likewise, linked after both.
-$(OBJDIR)/b64x_strict.o: $(STRICT_SRC) $(STRICT_BODY) $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_strict.o: $(STRICT_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # Their ragged-batch forms: likewise, linked after all three.
-$(OBJDIR)/b64x_lines_batch.o: $(BATCH_SRC) $(WRAP_BODY) $(STRICT_BODY) async_amd/csrc/b64x_lines_plan.h $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_lines_batch.o: $(BATCH_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)

@@ -50,7 +50,6 @@
 #include <string.h>
 
 #include "b64x.h"
-#include "b64x_lines_plan.h"
 #include "b64x_strict_body.h"
 #include "b64x_wrap_body.h"
 
@@ -129,7 +128,7 @@ DEV WrapArgs wrap_args(uint64_t len, const lines_plan::WrapPlan &p, const Call &
 
 __global__ __launch_bounds__(kBatchTH) void k_encode_lines_batch(
     const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off, uint32_t nbuf,
-    uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off, Call c, EncAlpha a)
+    uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off, Call c, Alpha a)
 {
     __shared__ uint8_t tab[64];
     __shared__ __attribute__((aligned(16))) uint8_t low16b[kLowRows * 16];
@@ -198,7 +197,7 @@ DEV void write_record(b64x_strict_result *dst, uint64_t out_len, uint64_t err_po
 }
 
 DEV StrictArgs strict_args(uint64_t W, const lines_plan::StrictPlan &p, const Call &c,
-                           const DecAlpha &a)
+                           const Alpha &a)
 {
     StrictArgs w = {};
     w.E = p.E;
@@ -227,7 +226,7 @@ template <bool WRAP>
 __global__ __launch_bounds__(kBatchTH) void k_decode_strict_batch(
     const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off, uint32_t nbuf,
     uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off, b64x_strict_result *res,
-    Call c, DecAlpha a)
+    Call c, Alpha a)
 {
     __shared__ uint8_t tab[256];
     __shared__ b64x_strict_result recs[kBatchWaves][kTailBufs];
@@ -323,15 +322,6 @@ __global__ __launch_bounds__(kBatchTH) void k_decode_strict_batch(
 
 // ---------------------------------------------------------------- host --
 
-int batch_status()
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return -ENODEV;
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    return -EIO;
-}
-
 // A persistent grid: a wave per buffer up to what the device holds at once.
 int batch_grid(uint32_t nbuf, uint32_t *grid)
 {
@@ -339,20 +329,13 @@ int batch_grid(uint32_t nbuf, uint32_t *grid)
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         cus <= 0) {
-        const int rc = batch_status();
+        const int rc = hip_status();
         return rc ? rc : -ENODEV;
     }
     const uint64_t want = ((uint64_t) nbuf + kBatchWaves - 1) / kBatchWaves;
     const uint64_t cap = (uint64_t) cus * kBlocksPerCU;
     *grid = (uint32_t) (want < cap ? want : cap);
     return 0;
-}
-
-Call call_of(const b64x_lines *f, const DecAlpha &a, bool decode)
-{
-    if (!f) return lines_plan::make_call(0, 0, nullptr, false, a.pad != 0, decode);
-    return lines_plan::make_call(f->line_len, f->sep_len, f->sep,
-                                 (f->flags & B64X_LINES_TRAILING) != 0, a.pad != 0, decode);
 }
 
 }  // namespace
@@ -365,17 +348,16 @@ int b64x_encode_lines_batch(const void *d_in, const uint64_t *d_in_off, uint32_t
 {
     if (nbuf == 0) return 0;
     if (!d_in || !d_in_off || !d_out || !d_out_off) return -EINVAL;
-    const DecAlpha a = dec_alpha(abc);
-    if (!fmt_ok(fmt, a)) return -EINVAL;
+    const Alpha a = lines_plan::make_alpha(abc);
+    if (!lines_plan::fmt_ok(fmt, a)) return -EINVAL;
     int rc = b64x_device_check();
     if (rc) return rc;
     uint32_t grid = 0;
     if ((rc = batch_grid(nbuf, &grid)) != 0) return rc;
-    const EncAlpha ea = {a.p62, a.p63, a.padc, a.pad};
     hipLaunchKernelGGL(k_encode_lines_batch, dim3(grid), dim3(kBatchTH), 0, (hipStream_t) stream,
                        (const uint8_t *) d_in, d_in_off, nbuf, (uint8_t *) d_out, d_out_off,
-                       call_of(fmt, a, false), ea);
-    return batch_status();
+                       lines_plan::make_call(fmt, a, false), a);
+    return hip_status();
 }
 
 int b64x_decode_strict_batch(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
@@ -385,14 +367,14 @@ int b64x_decode_strict_batch(const void *d_in, const uint64_t *d_in_off, uint32_
     if (nbuf == 0) return 0;
     if (!d_in || !d_in_off || !d_out || !d_out_off || !d_res || (((uintptr_t) d_res) & 7))
         return -EINVAL;
-    const DecAlpha a = dec_alpha(abc);
-    if (fmt && !fmt_ok(fmt, a)) return -EINVAL;
-    if (!alpha_ok(a)) return -EINVAL;
+    const Alpha a = lines_plan::make_alpha(abc);
+    if (fmt && !lines_plan::fmt_ok(fmt, a)) return -EINVAL;
+    if (!lines_plan::alpha_ok(a)) return -EINVAL;
     int rc = b64x_device_check();
     if (rc) return rc;
     uint32_t grid = 0;
     if ((rc = batch_grid(nbuf, &grid)) != 0) return rc;
-    const Call c = call_of(fmt, a, true);
+    const Call c = lines_plan::make_call(fmt, a, true);
     const uint8_t *in = (const uint8_t *) d_in;
     uint8_t *out = (uint8_t *) d_out;
     if (fmt)
@@ -401,7 +383,7 @@ int b64x_decode_strict_batch(const void *d_in, const uint64_t *d_in_off, uint32_
     else
         hipLaunchKernelGGL((k_decode_strict_batch<false>), dim3(grid), dim3(kBatchTH), 0,
                            (hipStream_t) stream, in, d_in_off, nbuf, out, d_out_off, d_res, c, a);
-    return batch_status();
+    return hip_status();
 }
 
 }  // extern "C"

@@ -33,10 +33,13 @@
 // and whose window lies inside the text; the rest of a row (the last group
 // and its pads, the unused-bits check, a short last line, the trailing
 // separator) is decoded bytewise, following the scalar procedure of b64x.h
-// literally, by extra blocks at the end of the same grid.  Buffers or strides
-// that are not dword aligned, L < 16, or a line length the 32-bit reciprocal
-// is not exact for take k_decode_strict_any: the same bytewise code for the
-// whole text.
+// literally, by extra blocks at the end of the same grid.  Where there is no
+// hot part, k_decode_strict_any takes the whole text with the same bytewise
+// code.
+//
+// Which of the two runs, its grid and its StrictArgs are the host's launch
+// plan (plan_strict of b64x_lines_plan.h, plain host C++ that is tested
+// without a GPU); what is here is validate, plan, launch.
 //
 // The record: a memset node fills it with ones (the empty key), the decode
 // kernel lowers the key and the lane that owns character E - 1 (which counts
@@ -44,14 +47,13 @@
 // turns the key into {out_len, err_pos, err}.  No host round trip, no
 // workspace, no state.
 //
-// The per-lane bodies (strict_lane, strict_bytes) and the structs they take
-// are in b64x_strict_body.h, shared with the ragged form
-// (b64x_lines_batch.hip), which keeps its records in LDS instead.
+// The per-lane bodies (strict_lane, strict_bytes) are in b64x_strict_body.h,
+// shared with the ragged form (b64x_lines_batch.hip), which keeps its records
+// in LDS instead.
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
 #include <stdint.h>
-#include <string.h>
 
 #include "b64x.h"
 #include "b64x_strict_body.h"
@@ -172,159 +174,22 @@ __global__ __launch_bounds__(kStrictTH) void k_strict_record(
 
 // ---------------------------------------------------------------- host --
 
-// Step 1 of the contract without the pad rules: the characters E a text of
-// nchars bytes holds.  false: no E exists (*E is then the characters of its
-// whole lines).
-bool text_chars(uint64_t nchars, const b64x_lines *f, uint64_t *E)
-{
-    *E = nchars;
-    if (!f || nchars == 0) return true;
-    const uint64_t L = f->line_len, s = f->sep_len, P = L + s;
-    const bool trailing = (f->flags & B64X_LINES_TRAILING) != 0;
-    const uint64_t m = trailing ? nchars : nchars + s;
-    if (m < nchars) {  // nchars + s wrapped round: no text is that long
-        *E = 0;
-        return false;
-    }
-    const uint64_t k = m / P, r = m % P;
-    *E = k * L + (r > s ? r - s : 0);
-    if (r != 0 && r <= s) return false;
-    // the encoder's length for E characters gives nchars back
-    const uint64_t lines = (*E + L - 1) / L;
-    return *E + s * (lines - (trailing ? 0 : 1)) == nchars;
-}
+using lines_plan::StrictLaunch;
 
-int hip_status()
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return -ENODEV;
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    return -EIO;
-}
-
-StrictArgs base_args(uint64_t nchars, uint64_t E, const DecAlpha &a, const b64x_lines *f,
-                     uint64_t in_stride, uint64_t out_stride)
-{
-    StrictArgs w;
-    memset(&w, 0, sizeof w);
-    w.E = E;
-    w.W = nchars;
-    w.in_stride = in_stride;
-    w.out_stride = out_stride;
-    w.a = a;
-    if (f) {
-        w.L = f->line_len;
-        w.s = f->sep_len;
-        w.P = w.L + w.s;
-        w.trailing = (f->flags & B64X_LINES_TRAILING) ? 1 : 0;
-        for (uint32_t i = 0; i < w.s; i++) {
-            w.sep |= (uint32_t) f->sep[i] << (8 * i);
-            w.sep_mask |= 0xFFu << (8 * i);
-        }
-    }
-    if (E >= 2) {
-        w.off_e1 = char_offset(E - 1, w);
-        w.off_e2 = char_offset(E - 2, w);
-    }
-    return w;
-}
-
-// The line length's reciprocals, if they are exact for this call: the 32-bit
-// one for every value below `max32`, the 64-bit one for every character index.
-bool set_reciprocals(StrictArgs &w, uint64_t max32)
-{
-    if (w.L < kLaneChars) return false;
-    w.magic_l = (uint32_t) ((0xFFFFFFFFull + w.L) / w.L);
-    const uint64_t err = (uint64_t) w.magic_l * w.L - (1ull << 32);  // < L
-    if (max32 >= (1ull << 32) || max32 * err >= (1ull << 32)) return false;
-    w.m64 = ~0ull / w.L + 1;
-    return w.E <= ~0ull / w.L;  // index * (m64 L - 2^64) < 2^64
-}
-
-// Lanes [0, n) of a row are hot: their characters lie below E - 4 (the last
-// group, with the pads and the unused bits, is the tail's) and their windows
-// inside the text.
-uint64_t count_hot_lanes(const StrictArgs &w)
-{
-    if (w.E < 4 + kLaneChars) return 0;
-    uint64_t n = (w.E - 4) / kLaneChars;
-    const uint64_t win = w.s ? 24 : 16;
-    while (n > 0 && (char_offset((n - 1) * kLaneChars, w) & ~(uint64_t) 3) + win > w.W) n--;
-    return n;
-}
-
-enum PlanKind { kPlanAny, kPlanOne, kPlanRows };
-
-struct Plan {
-    PlanKind kind;
-    uint32_t grid;
-    StrictArgs w;
-};
-
-// How a call of `nbuf` rows runs (w: base_args).
-Plan make_plan(const void *d_in, const void *d_out, uint32_t nbuf, StrictArgs w)
-{
-    Plan p;
-    const uint64_t per_row = (w.E + kLaneChars - 1) / kLaneChars;
-    const bool aligned = ((((uintptr_t) d_in) | ((uintptr_t) d_out)) & 3) == 0 &&
-                         (nbuf == 1 || ((w.in_stride | w.out_stride) & 3) == 0);
-    const uint64_t hot = aligned ? count_hot_lanes(w) : 0;
-    if (nbuf == 1 && hot > 0 && (!w.s || set_reciprocals(w, (uint64_t) w.L + kTileChars))) {
-        w.hot_lanes = w.hot_slots = hot;
-        w.tail_lanes = w.tail_slots = per_row - hot;
-        const uint64_t tiles = (hot + kStrictTH - 1) / kStrictTH;
-        const uint64_t grid = tiles + (w.tail_slots + kStrictTH - 1) / kStrictTH;
-        if (grid < (1ull << 31)) {
-            w.hot_tiles = (uint32_t) tiles;
-            p.kind = kPlanOne;
-            p.grid = (uint32_t) grid;
-            p.w = w;
-            return p;
-        }
-    }
-    if (nbuf > 1 && hot > 1 && w.W < (1u << 28) && (!w.s || set_reciprocals(w, w.E))) {
-        w.hot_lanes = hot;
-        w.hot_slots = hot * nbuf;
-        w.tail_lanes = per_row - hot;
-        w.tail_slots = w.tail_lanes * nbuf;
-        w.hot_lanes32 = (uint32_t) hot;
-        w.magic_hl = (uint32_t) ((0xFFFFFFFFull + hot) / hot);
-        w.m64_hl = ~0ull / hot + 1;
-        const uint64_t err = (uint64_t) w.magic_hl * hot - (1ull << 32);
-        const uint64_t tiles = (w.hot_slots + kStrictTH - 1) / kStrictTH;
-        const uint64_t grid = tiles + (w.tail_slots + kStrictTH - 1) / kStrictTH;
-        // exact: the lane's slot below hot + kStrictTH, the tile's below hot_slots
-        if ((hot + kStrictTH) * err < (1ull << 32) && w.hot_slots <= ~0ull / hot &&
-            grid < (1ull << 31)) {
-            w.hot_tiles = (uint32_t) tiles;
-            p.kind = kPlanRows;
-            p.grid = (uint32_t) grid;
-            p.w = w;
-            return p;
-        }
-    }
-    w.hot_lanes = w.hot_slots = w.tail_lanes = w.tail_slots = 0;
-    w.hot_tiles = 0;
-    uint64_t grid = (per_row * nbuf + kStrictTH - 1) / kStrictTH;
-    if (grid > (1u << 20)) grid = 1u << 20;
-    p.kind = kPlanAny;
-    p.grid = (uint32_t) grid;
-    p.w = w;
-    return p;
-}
+uint32_t low4(const void *p) { return (uint32_t) ((uintptr_t) p & 15); }
 
 int launch(const void *d_in, void *d_out, b64x_strict_result *d_res, uint32_t nbuf,
-           const Plan &p, hipStream_t st)
+           const StrictLaunch &p, hipStream_t st)
 {
     const uint8_t *in = (const uint8_t *) d_in;
     uint8_t *out = (uint8_t *) d_out;
     const dim3 g(p.grid), b(kStrictTH);
-    if (p.kind == kPlanAny)
+    const bool rows = nbuf > 1;
+    if (p.kind == lines_plan::kAny)
         hipLaunchKernelGGL(k_decode_strict_any, g, b, 0, st, in, out, d_res, nbuf, p.w);
-    else if (p.kind == kPlanOne && p.w.s)
+    else if (!rows && p.w.s)
         hipLaunchKernelGGL((k_decode_strict<false, true>), g, b, 0, st, in, out, d_res, p.w);
-    else if (p.kind == kPlanOne)
+    else if (!rows)
         hipLaunchKernelGGL((k_decode_strict<false, false>), g, b, 0, st, in, out, d_res, p.w);
     else if (p.w.s)
         hipLaunchKernelGGL((k_decode_strict<true, true>), g, b, 0, st, in, out, d_res, p.w);
@@ -339,12 +204,13 @@ int decode_strict(const void *d_in, uint64_t in_stride, uint64_t nchars, uint32_
                   const b64x_alphabet *abc, const b64x_lines *fmt, bool strided, void *stream)
 {
     if (!d_in || !d_out || !d_res || (((uintptr_t) d_res) & 7)) return -EINVAL;
-    const DecAlpha a = dec_alpha(abc);
-    if (fmt && !fmt_ok(fmt, a)) return -EINVAL;
-    if (!alpha_ok(a)) return -EINVAL;
-    uint64_t E;
-    bool has_e = text_chars(nchars, fmt, &E);
-    if (strided && (in_stride < nchars || out_stride < (E + 3) / 4 * 3)) return -EINVAL;
+    const Alpha a = lines_plan::make_alpha(abc);
+    if (fmt && !lines_plan::fmt_ok(fmt, a)) return -EINVAL;
+    if (!lines_plan::alpha_ok(a)) return -EINVAL;
+    const StrictLaunch p =
+        lines_plan::plan_strict(nchars, nbuf, lines_plan::make_call(fmt, a, true), a, low4(d_in),
+                                low4(d_out), in_stride, out_stride);
+    if (strided && (in_stride < nchars || out_stride < (p.w.E + 3) / 4 * 3)) return -EINVAL;
     if (nbuf == 0) return 0;
     const int rc = b64x_device_check();
     if (rc) return rc;
@@ -354,18 +220,15 @@ int decode_strict(const void *d_in, uint64_t in_stride, uint64_t nchars, uint32_
         if (hipMemsetAsync(d_res, 0, res_bytes, st) != hipSuccess) return hip_status();
         return 0;
     }
-    if (has_e && (a.pad ? E % 4 != 0 : E % 4 == 1)) has_e = false;
-    const StrictArgs w = base_args(nchars, E, a, fmt, in_stride, out_stride);
-    const uint32_t rgrid = (nbuf + kStrictTH - 1) / kStrictTH;
-    if (has_e) {
+    if (!p.length_error) {
         // the empty key in every record, then the decode lowers it
         if (hipMemsetAsync(d_res, 0xFF, res_bytes, st) != hipSuccess) return hip_status();
-        const Plan p = make_plan(d_in, d_out, nbuf, w);
         const int rc2 = launch(d_in, d_out, d_res, nbuf, p, st);
         if (rc2) return rc2;
     }
+    const uint32_t rgrid = (nbuf + kStrictTH - 1) / kStrictTH;
     hipLaunchKernelGGL(k_strict_record, dim3(rgrid), dim3(kStrictTH), 0, st, d_res, nbuf,
-                       has_e ? 0u : 1u, nchars);
+                       p.length_error, nchars);
     return hip_status();
 }
 
@@ -375,10 +238,12 @@ extern "C" {
 
 uint64_t b64x_strict_decoded_cap(uint64_t nchars, const b64x_lines *fmt)
 {
-    if (fmt && (fmt->line_len == 0 || fmt->sep_len < 1 || fmt->sep_len > 4)) return 0;
-    uint64_t E;
-    text_chars(nchars, fmt, &E);
-    return (E + 3) / 4 * 3;
+    // a pitch past 32 bits, which no call accepts, has no Call: 0 as well (b64x.h)
+    if (fmt && (fmt->line_len == 0 || fmt->sep_len < 1 || fmt->sep_len > 4 ||
+                (uint64_t) fmt->line_len + fmt->sep_len > 0xFFFFFFFFull))
+        return 0;
+    const lines_plan::Call c = lines_plan::make_call(fmt, lines_plan::make_alpha(nullptr), true);
+    return (lines_plan::strict_plan(nchars, c, false).E + 3) / 4 * 3;
 }
 
 int b64x_decode_strict_dev(const void *d_in, uint64_t nchars, void *d_out,

@@ -1,60 +1,24 @@
-// The per-lane bodies of the strict decode and the structs they take, shared
-// by b64x_strict.hip (b64x_decode_strict_dev / _strided) and
-// b64x_lines_batch.hip (b64x_decode_strict_batch): strict_lane() decodes and
-// checks 16 characters of a row's hot part, strict_bytes() up to 16 characters
-// of its tail as the scalar procedure of b64x.h states it.  Layout:
-// b64x_strict.hip's header and DESIGN.md §5, "k_decode_strict".
+// The per-lane bodies of the strict decode, shared by b64x_strict.hip
+// (b64x_decode_strict_dev / _strided) and b64x_lines_batch.hip
+// (b64x_decode_strict_batch): strict_lane() decodes and checks 16 characters
+// of a row's hot part, strict_bytes() up to 16 characters of its tail as the
+// scalar procedure of b64x.h states it.  The structs they take are those of
+// b64x_lines_plan.h.  Layout: b64x_strict.hip's header and DESIGN.md §5,
+// "k_decode_strict".
 #ifndef ASYNC_AMD_B64X_STRICT_BODY_H
 #define ASYNC_AMD_B64X_STRICT_BODY_H
 
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
 #include <string.h>
 
 #include "b64x.h"
-#include "b64x_block_sync.h"
-
-#define HD __host__ __device__ __forceinline__
+#include "b64x_lines_dev.h"
 
 namespace {
 
-constexpr uint32_t kStrictTH = 256;                  // lanes per block
+constexpr uint32_t kStrictTH = lines_plan::kBlockLanes;  // lanes per block
 constexpr uint32_t kLaneChars = 16;                  // characters per lane (12 bytes out)
 constexpr uint32_t kTileChars = kStrictTH * kLaneChars;
 constexpr uint64_t kNoKey = ~0ull;
-
-typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u32x3a4 __attribute__((ext_vector_type(3), aligned(4)));
-typedef uint32_t u32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
-
-struct DecAlpha {
-    uint32_t p62, p63, padc, pad;
-};
-
-// Everything a kernel needs to know about one call; travels as a kernel
-// argument (capture-safe, nothing on the device to set up).
-struct StrictArgs {
-    uint64_t E;           // characters per row
-    uint64_t W;           // text bytes per row
-    uint64_t in_stride, out_stride;
-    uint64_t off_e1, off_e2;  // row offsets of characters E - 1 and E - 2
-    uint64_t hot_lanes;   // per row: lanes [0, hot_lanes) take the hot path
-    uint64_t hot_slots;   // hot_lanes * rows
-    uint64_t tail_lanes;  // per row: the lanes of characters [16 hot_lanes, E)
-    uint64_t tail_slots;  // tail_lanes * rows
-    uint64_t m64;         // floor(2^64 / L) + 1
-    uint64_t m64_hl;      // floor(2^64 / hot_lanes) + 1  (rows)
-    uint32_t hot_tiles;   // grid blocks that run the hot path
-    uint32_t L, P, s;     // line length, pitch L + s, separator length (plain: 0)
-    uint32_t sep;         // the separator, little-endian, unused bytes zero
-    uint32_t sep_mask;    // 0xFF for each of its s bytes
-    uint32_t magic_l;     // ceil(2^32 / L)
-    uint32_t magic_hl;    // ceil(2^32 / hot_lanes)  (rows)
-    uint32_t hot_lanes32;
-    uint32_t trailing;
-    DecAlpha a;
-};
 
 // ------------------------------------------------------------ primitives --
 
@@ -126,7 +90,7 @@ HD void store12(uint8_t *dst, uint32_t a, uint32_t b, uint32_t c)
 HD uint64_t make_key(uint64_t off, uint32_t kind) { return (off << 3) | kind; }
 
 // byte -> sextet; 0x80: not one of the 64; 0xC0: the pad character (with pad)
-HD uint32_t classify(uint32_t b, const DecAlpha &a)
+HD uint32_t classify(uint32_t b, const Alpha &a)
 {
     if (b - 'A' < 26u) return b - 'A';
     if (b - 'a' < 26u) return b - 'a' + 26;
@@ -134,11 +98,6 @@ HD uint32_t classify(uint32_t b, const DecAlpha &a)
     if (b == a.p62) return 62;
     if (b == a.p63) return 63;
     return a.pad && b == a.padc ? 0xC0u : 0x80u;
-}
-
-HD uint64_t char_offset(uint64_t e, const StrictArgs &w)
-{
-    return w.s ? e / w.L * w.P + e % w.L : e;
 }
 
 // D: the row's data characters, E less the 0..2 pad characters it ends in
@@ -387,49 +346,9 @@ HD void finish_record(b64x_strict_result *r)
     r->reserved = 0;
 }
 
-__device__ __forceinline__ void build_dec_table(uint8_t *tab, const DecAlpha &a)
+DEV void build_dec_table(uint8_t *tab, const Alpha &a)
 {
     tab[threadIdx.x] = (uint8_t) classify(threadIdx.x, a);  // kStrictTH == 256
-}
-
-// ------------------------------------------------- argument validation --
-
-DecAlpha dec_alpha(const b64x_alphabet *abc)
-{
-    DecAlpha a;
-    const char p62 = abc ? abc->pos62 : (char) -1;
-    const char p63 = abc ? abc->pos63 : (char) -1;
-    const char pc = abc ? abc->padchar : (char) -1;
-    a.p62 = (uint8_t) (p62 == (char) -1 ? '+' : p62);
-    a.p63 = (uint8_t) (p63 == (char) -1 ? '/' : p63);
-    a.padc = (uint8_t) (pc == (char) -1 ? '=' : pc);
-    a.pad = abc ? (abc->pad ? 1 : 0) : 1;
-    return a;
-}
-
-bool is_alnum(uint32_t c) { return c - 'A' < 26u || c - 'a' < 26u || c - '0' < 10u; }
-
-// The decoder needs what the encoder takes for granted: 64 distinct
-// characters and a pad character that is none of them.
-bool alpha_ok(const DecAlpha &a)
-{
-    if (a.p62 == a.p63 || is_alnum(a.p62) || is_alnum(a.p63)) return false;
-    return !(a.pad && (is_alnum(a.padc) || a.padc == a.p62 || a.padc == a.p63));
-}
-
-// b64x_encode_lines_dev's rules, in its order.
-bool fmt_ok(const b64x_lines *f, const DecAlpha &a)
-{
-    if (!f) return false;
-    if (f->line_len == 0 || f->line_len % 4 != 0) return false;
-    if (f->sep_len < 1 || f->sep_len > 4) return false;
-    if (f->flags & ~B64X_LINES_TRAILING) return false;
-    if ((uint64_t) f->line_len + f->sep_len > 0xFFFFFFFFull) return false;
-    for (uint32_t i = 0; i < f->sep_len; i++) {
-        const uint32_t c = f->sep[i];
-        if (is_alnum(c) || c == a.p62 || c == a.p63) return false;
-    }
-    return true;
 }
 
 }  // namespace

@@ -27,17 +27,18 @@
 // with 20 readable bytes behind their first group; the rest of the row (the
 // last blocks: partial group, padding, a short last line and its separator)
 // is written bytewise by extra blocks at the end of the same grid, dense, so
-// that no hot wave diverges into the bytewise code.  Buffers that are not
-// dword aligned, L < 16, or a line pitch the 32-bit reciprocal is not exact
-// for take k_encode_lines_any: the same bytewise code for the whole text.
+// that no hot wave diverges into the bytewise code.  Where there is no hot
+// part, k_encode_lines_any takes the whole text with the same bytewise code.
 //
-// The per-lane bodies (wrap_block, wrap_bytes) and the structs they take are
-// in b64x_wrap_body.h, shared with the ragged form (b64x_lines_batch.hip).
+// Which of the two runs, its grid and its WrapArgs are the host's launch plan
+// (plan_wrap_one, plan_wrap_rows of b64x_lines_plan.h, plain host C++ that is
+// tested without a GPU); what is here is validate, plan, launch.  The
+// per-lane bodies (wrap_block, wrap_bytes) are in b64x_wrap_body.h, shared
+// with the ragged form (b64x_lines_batch.hip).
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
 #include <stdint.h>
-#include <string.h>
 
 #include <type_traits>
 
@@ -50,7 +51,7 @@ namespace {
 // a row's text (row-relative, no alignment assumed) bytewise, grid-stride.
 __global__ __launch_bounds__(kWrapTH) void k_encode_lines_any(
     const uint8_t *__restrict__ in, uint8_t *__restrict__ out, uint32_t nbuf, WrapArgs w,
-    EncAlpha a)
+    Alpha a)
 {
     __shared__ uint8_t tab[64];
     build_enc_table(tab, a);
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(kWrapTH) void k_encode_lines_any(
 // BIG when its positions need 64 bits.
 template <bool ROWS, bool BIG>
 __global__ __launch_bounds__(kWrapTH) void k_encode_lines(
-    const uint8_t *__restrict__ in, uint8_t *__restrict__ out, WrapArgs w, EncAlpha a)
+    const uint8_t *__restrict__ in, uint8_t *__restrict__ out, WrapArgs w, Alpha a)
 {
     typedef typename std::conditional<BIG, uint64_t, uint32_t>::type IDX;
     __shared__ uint8_t tab[64];
@@ -122,124 +123,35 @@ __global__ __launch_bounds__(kWrapTH) void k_encode_lines(
 
 // ---------------------------------------------------------------- host --
 
-EncAlpha enc_alpha(const b64x_alphabet *abc)
-{
-    EncAlpha a;
-    const char p62 = abc ? abc->pos62 : (char) -1;
-    const char p63 = abc ? abc->pos63 : (char) -1;
-    const char pc = abc ? abc->padchar : (char) -1;
-    a.p62 = (uint8_t) (p62 == (char) -1 ? '+' : p62);
-    a.p63 = (uint8_t) (p63 == (char) -1 ? '/' : p63);
-    a.padc = (uint8_t) (pc == (char) -1 ? '=' : pc);
-    a.pad = abc ? (abc->pad ? 1 : 0) : 1;
-    return a;
-}
+using lines_plan::WrapLaunch;
 
-bool fmt_ok(const b64x_lines *f, const EncAlpha &a)
-{
-    if (!f) return false;
-    if (f->line_len == 0 || f->line_len % 4 != 0) return false;
-    if (f->sep_len < 1 || f->sep_len > 4) return false;
-    if (f->flags & ~B64X_LINES_TRAILING) return false;
-    if ((uint64_t) f->line_len + f->sep_len > 0xFFFFFFFFull) return false;
-    for (uint32_t i = 0; i < f->sep_len; i++) {
-        const uint32_t c = f->sep[i];
-        if (c - 'A' < 26u || c - 'a' < 26u || c - '0' < 10u || c == a.p62 || c == a.p63)
-            return false;
-    }
-    return true;
-}
+uint32_t low4(const void *p) { return (uint32_t) ((uintptr_t) p & 15); }
 
-uint64_t wrapped_len(uint64_t E, const b64x_lines *f)
+// kAny: all nbuf rows; kHot: the rows the plan covers (one buffer, or all but
+// the last row).
+int launch(const void *d_in, void *d_out, uint32_t nbuf, const WrapLaunch &p, const Alpha &a,
+           void *stream)
 {
-    if (E == 0) return 0;
-    const uint64_t lines = (E + f->line_len - 1) / f->line_len;
-    return E + (uint64_t) f->sep_len * (lines - ((f->flags & B64X_LINES_TRAILING) ? 0 : 1));
-}
-
-int hip_status()
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return -ENODEV;
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    return -EIO;
-}
-
-// Row offset of character e (e < E, or e == E inside a short last line).
-uint64_t char_offset(uint64_t e, uint32_t L, uint32_t P) { return e / L * P + e % L; }
-
-WrapArgs base_args(uint64_t len, const EncAlpha &a, const b64x_lines *f, uint64_t in_stride,
-                   uint64_t out_stride)
-{
-    WrapArgs w;
-    memset(&w, 0, sizeof w);
-    w.len = len;
-    w.E = b64x_encoded_len(len, a.pad);
-    w.W = wrapped_len(w.E, f);
-    w.L = f->line_len;
-    w.s = f->sep_len;
-    w.P = w.L + w.s;
-    w.full_lines = w.E / w.L;
-    w.last_len = (uint32_t) (w.E % w.L);
-    for (uint32_t i = 0; i < w.s; i++) w.sep |= (uint32_t) f->sep[i] << (8 * i);
-    w.in_stride = in_stride;
-    w.out_stride = out_stride;
-    return w;
-}
-
-// The line pitch's reciprocals, if they are exact for this call: the 32-bit
-// one for every value below `max32`, the 64-bit one for every row offset.
-bool set_reciprocals(WrapArgs &w, uint64_t max32)
-{
-    if (w.L < 16 || w.P > (1u << 24)) return false;
-    w.magic_p = (uint32_t) ((0xFFFFFFFFull + w.P) / w.P);
-    const uint64_t err = (uint64_t) w.magic_p * w.P - (1ull << 32);  // < P
-    if (max32 >= (1ull << 32) || max32 * err >= (1ull << 32)) return false;
-    w.m64 = ~0ull / w.P + 1;
-    return w.W <= ~0ull / w.P;  // offset * (m64 P - 2^64) < 2^64
-}
-
-int launch_any(const void *d_in, void *d_out, uint32_t nbuf, const WrapArgs &w,
-               const EncAlpha &a, void *stream)
-{
-    const uint64_t slots = (w.W + 15) / 16 * nbuf;
-    uint64_t grid = (slots + kWrapTH - 1) / kWrapTH;
-    if (grid > (1u << 20)) grid = 1u << 20;
-    hipLaunchKernelGGL(k_encode_lines_any, dim3((uint32_t) grid), dim3(kWrapTH), 0,
-                       (hipStream_t) stream, (const uint8_t *) d_in, (uint8_t *) d_out, nbuf, w, a);
+    const uint8_t *in = (const uint8_t *) d_in;
+    uint8_t *out = (uint8_t *) d_out;
+    const dim3 g(p.grid), b(kWrapTH);
+    const hipStream_t st = (hipStream_t) stream;
+    if (p.kind == lines_plan::kAny)
+        hipLaunchKernelGGL(k_encode_lines_any, g, b, 0, st, in, out, nbuf, p.w, a);
+    else if (nbuf > 1)
+        hipLaunchKernelGGL((k_encode_lines<true, false>), g, b, 0, st, in, out, p.w, a);
+    else if (p.w.W < (1ull << 32))
+        hipLaunchKernelGGL((k_encode_lines<false, false>), g, b, 0, st, in, out, p.w, a);
+    else
+        hipLaunchKernelGGL((k_encode_lines<false, true>), g, b, 0, st, in, out, p.w, a);
     return hip_status();
 }
 
-// One buffer.
-int launch_one(const void *d_in, uint64_t n, void *d_out, const EncAlpha &a,
-               const b64x_lines *f, void *stream)
+int launch_one(const void *d_in, uint64_t n, void *d_out, const Alpha &a,
+               const lines_plan::Call &c, void *stream)
 {
-    WrapArgs w = base_args(n, a, f, 0, 0);
-    const bool aligned = (((uintptr_t) d_in) & 3) == 0 && (((uintptr_t) d_out) & 15) == 0;
-    if (aligned && n >= 17 && set_reciprocals(w, (uint64_t) w.P + kWrapTile)) {
-        // hot: the blocks wholly below the first character whose group does
-        // not have 20 readable bytes behind its first byte
-        const uint64_t e_hot = (n - 17) / 3 * 4;
-        w.hot_blocks = char_offset(e_hot, w.L, w.P) / 16;
-        const uint64_t tiles = (w.hot_blocks + kWrapTH - 1) / kWrapTH;
-        w.tail_blocks = w.tail_slots = (w.W - 16 * w.hot_blocks + 15) / 16;
-        const uint64_t grid = tiles + (w.tail_slots + kWrapTH - 1) / kWrapTH;
-        if (w.hot_blocks > 0 && grid < (1ull << 31)) {
-            w.hot_slots = w.hot_blocks;
-            w.hot_tiles = (uint32_t) tiles;
-            if (w.W < (1ull << 32))
-                hipLaunchKernelGGL((k_encode_lines<false, false>), dim3((uint32_t) grid),
-                                   dim3(kWrapTH), 0, (hipStream_t) stream,
-                                   (const uint8_t *) d_in, (uint8_t *) d_out, w, a);
-            else
-                hipLaunchKernelGGL((k_encode_lines<false, true>), dim3((uint32_t) grid),
-                                   dim3(kWrapTH), 0, (hipStream_t) stream,
-                                   (const uint8_t *) d_in, (uint8_t *) d_out, w, a);
-            return hip_status();
-        }
-    }
-    return launch_any(d_in, d_out, 1, w, a, stream);
+    return launch(d_in, d_out, 1, lines_plan::plan_wrap_one(n, c, low4(d_in), low4(d_out)), a,
+                  stream);
 }
 
 }  // namespace
@@ -249,7 +161,9 @@ extern "C" {
 uint64_t b64x_encoded_lines_len(uint64_t n, bool pad, const b64x_lines *fmt)
 {
     if (!fmt || fmt->line_len == 0 || fmt->sep_len > 4) return 0;
-    return wrapped_len(b64x_encoded_len(n, pad), fmt);
+    const lines_plan::Call c = lines_plan::make_call(
+        fmt->line_len, fmt->sep_len, fmt->sep, (fmt->flags & B64X_LINES_TRAILING) != 0, pad, false);
+    return lines_plan::wrap_plan(n, c, false).W;
 }
 
 int b64x_encode_lines_dev(const void *d_in, uint64_t n, void *d_out,
@@ -257,11 +171,11 @@ int b64x_encode_lines_dev(const void *d_in, uint64_t n, void *d_out,
 {
     if (n == 0) return 0;
     if (!d_in || !d_out) return -EINVAL;
-    const EncAlpha a = enc_alpha(abc);
-    if (!fmt_ok(fmt, a)) return -EINVAL;
+    const Alpha a = lines_plan::make_alpha(abc);
+    if (!lines_plan::fmt_ok(fmt, a)) return -EINVAL;
     const int rc = b64x_device_check();
     if (rc) return rc;
-    return launch_one(d_in, n, d_out, a, fmt, stream);
+    return launch_one(d_in, n, d_out, a, lines_plan::make_call(fmt, a, false), stream);
 }
 
 int b64x_encode_lines_strided(const void *d_in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
@@ -270,49 +184,22 @@ int b64x_encode_lines_strided(const void *d_in, uint64_t in_stride, uint64_t len
 {
     if (nbuf == 0 || len == 0) return 0;
     if (!d_in || !d_out) return -EINVAL;
-    const EncAlpha a = enc_alpha(abc);
-    if (!fmt_ok(fmt, a)) return -EINVAL;
-    WrapArgs w = base_args(len, a, fmt, in_stride, out_stride);
-    if (in_stride < len || out_stride < w.W) return -EINVAL;
+    const Alpha a = lines_plan::make_alpha(abc);
+    if (!lines_plan::fmt_ok(fmt, a)) return -EINVAL;
+    const lines_plan::Call c = lines_plan::make_call(fmt, a, false);
+    const WrapLaunch p =
+        nbuf == 1 ? lines_plan::plan_wrap_one(len, c, low4(d_in), low4(d_out))
+                  : lines_plan::plan_wrap_rows(len, nbuf, c, low4(d_in), low4(d_out), in_stride,
+                                               out_stride);
+    if (in_stride < len || out_stride < p.w.W) return -EINVAL;
     const int rc = b64x_device_check();
     if (rc) return rc;
-    if (nbuf == 1) return launch_one(d_in, len, d_out, a, fmt, stream);
-    // Rows at dword-aligned addresses: every row but the last takes the hot
-    // path up to the first character of an incomplete group (a window may
-    // read into the next row, so the last row goes alone, as one buffer).
-    const uint32_t hot_rows = nbuf - 1;
-    const bool aligned =
-        ((((uintptr_t) d_in) | ((uintptr_t) d_out) | in_stride | out_stride) & 3) == 0;
-    if (aligned && len >= 20 && w.W < (1u << 28) && set_reciprocals(w, w.W)) {
-        const uint64_t e_c = len / 3 * 4;  // characters of complete groups
-        const uint64_t hot_end = (e_c == w.E && w.last_len == 0) ? w.W : char_offset(e_c, w.L, w.P);
-        w.hot_blocks = hot_end / 16;
-        w.hot_slots = w.hot_blocks * hot_rows;
-        w.tail_blocks = (w.W - 16 * w.hot_blocks + 15) / 16;
-        w.tail_slots = w.tail_blocks * hot_rows;
-        const uint64_t tiles = (w.hot_slots + kWrapTH - 1) / kWrapTH;
-        const uint64_t grid = tiles + (w.tail_slots + kWrapTH - 1) / kWrapTH;
-        if (w.hot_blocks > 1 && grid < (1ull << 31)) {
-            w.hot_blocks32 = (uint32_t) w.hot_blocks;
-            w.magic_hb = (uint32_t) ((0xFFFFFFFFull + w.hot_blocks) / w.hot_blocks);
-            w.m64_hb = ~0ull / w.hot_blocks + 1;
-            const uint64_t err = (uint64_t) w.magic_hb * w.hot_blocks - (1ull << 32);
-            // exact: the lane's slot below hot_blocks + kWrapTH, the tile's below hot_slots
-            if ((w.hot_blocks + kWrapTH) * err < (1ull << 32) &&
-                w.hot_slots <= ~0ull / w.hot_blocks) {
-                w.hot_tiles = (uint32_t) tiles;
-                hipLaunchKernelGGL((k_encode_lines<true, false>), dim3((uint32_t) grid),
-                                   dim3(kWrapTH), 0, (hipStream_t) stream,
-                                   (const uint8_t *) d_in, (uint8_t *) d_out, w, a);
-                const int rc2 = hip_status();
-                if (rc2) return rc2;
-                return launch_one((const uint8_t *) d_in + (uint64_t) hot_rows * in_stride, len,
-                                  (uint8_t *) d_out + (uint64_t) hot_rows * out_stride, a, fmt,
-                                  stream);
-            }
-        }
-    }
-    return launch_any(d_in, d_out, nbuf, w, a, stream);
+    const int rc2 = launch(d_in, d_out, nbuf, p, a, stream);
+    if (rc2 || nbuf == 1 || p.kind == lines_plan::kAny) return rc2;
+    // the rows' hot kernel leaves the last row out: it goes as one buffer
+    const uint64_t last = nbuf - 1;
+    return launch_one((const uint8_t *) d_in + last * in_stride, len,
+                      (uint8_t *) d_out + last * out_stride, a, c, stream);
 }
 
 }  // extern "C"

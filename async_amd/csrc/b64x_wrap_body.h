@@ -1,55 +1,21 @@
-// The per-lane bodies of the line-wrapped encode and the structs they take,
-// shared by b64x_wrap.hip (b64x_encode_lines_dev / _strided) and
-// b64x_lines_batch.hip (b64x_encode_lines_batch): wrap_block() writes one
-// 16-byte output block of a row's hot part, wrap_bytes() up to 16 bytes of
-// its tail.  Layout: b64x_wrap.hip's header and DESIGN.md §5, "k_encode_lines".
+// The per-lane bodies of the line-wrapped encode, shared by b64x_wrap.hip
+// (b64x_encode_lines_dev / _strided) and b64x_lines_batch.hip
+// (b64x_encode_lines_batch): wrap_block() writes one 16-byte output block of a
+// row's hot part, wrap_bytes() up to 16 bytes of its tail.  The structs they
+// take are those of b64x_lines_plan.h.  Layout: b64x_wrap.hip's header and
+// DESIGN.md §5, "k_encode_lines".
 #ifndef ASYNC_AMD_B64X_WRAP_BODY_H
 #define ASYNC_AMD_B64X_WRAP_BODY_H
 
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
-
-#include "b64x_block_sync.h"
-
-#define DEV __device__ __forceinline__
+#include "b64x_lines_dev.h"
 
 namespace {
 
-constexpr uint32_t kWrapTH = 256;      // lanes per block: one 16-byte block each
-constexpr uint32_t kWrapTile = kWrapTH * 16;  // output bytes per hot tile
-
-typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-struct EncAlpha {
-    uint32_t p62, p63, padc, pad;
-};
-
-// Everything a kernel needs to know about one call; travels as a kernel
-// argument (capture-safe, nothing on the device to set up).
-struct WrapArgs {
-    uint64_t len;         // input bytes per row
-    uint64_t E;           // characters per row
-    uint64_t W;           // wrapped bytes per row
-    uint64_t full_lines;  // E / L
-    uint64_t in_stride, out_stride;
-    uint64_t hot_blocks;  // per row: blocks [0, hot_blocks) take the hot path
-    uint64_t hot_slots;   // hot_blocks * hot rows
-    uint64_t tail_blocks; // per row: 16-byte pieces of [16 hot_blocks, W)
-    uint64_t tail_slots;  // tail_blocks * hot rows
-    uint64_t m64;         // floor(2^64 / P) + 1
-    uint64_t m64_hb;      // floor(2^64 / hot_blocks) + 1  (rows)
-    uint32_t hot_tiles;   // grid blocks that run the hot path
-    uint32_t L, P, s;     // line length, pitch L + s, separator length
-    uint32_t sep;         // the separator, little-endian, unused bytes zero
-    uint32_t last_len;    // E mod L
-    uint32_t magic_p;     // ceil(2^32 / P)
-    uint32_t magic_hb;    // ceil(2^32 / hot_blocks)  (rows)
-    uint32_t hot_blocks32;
-};
+constexpr uint32_t kWrapTH = lines_plan::kBlockLanes;  // lanes per block: one 16-byte block each
+constexpr uint32_t kWrapTile = kWrapTH * 16;            // output bytes per hot tile
 
 // src/base64encoder.c:26-27 (62-char map) + :49-59 (62 -> pos62, 63 -> pos63)
-DEV uint32_t enc_char(uint32_t v, const EncAlpha &a)
+DEV uint32_t enc_char(uint32_t v, const Alpha &a)
 {
     return v < 26 ? 'A' + v
          : v < 52 ? 'a' + (v - 26)
@@ -57,7 +23,7 @@ DEV uint32_t enc_char(uint32_t v, const EncAlpha &a)
          : v == 62 ? a.p62 : a.p63;
 }
 
-DEV void build_enc_table(uint8_t *tab, const EncAlpha &a)
+DEV void build_enc_table(uint8_t *tab, const Alpha &a)
 {
     if (threadIdx.x < 64) tab[threadIdx.x] = (uint8_t) enc_char(threadIdx.x, a);
 }
@@ -97,7 +63,7 @@ DEV void build_splice_tables(uint8_t *low16, uint8_t *sep16, uint32_t sep, uint3
 // characters.  Gathered in registers and stored as whole dwords where the
 // destination is dword aligned, the rest bytewise.
 DEV void wrap_bytes(const uint8_t *tab, const uint8_t *in, uint8_t *out, uint64_t q0,
-                    uint32_t cnt, const WrapArgs &w, const EncAlpha &a)
+                    uint32_t cnt, const WrapArgs &w, const Alpha &a)
 {
     uint64_t k = q0 / w.P;
     uint32_t c = (uint32_t) (q0 - k * w.P);

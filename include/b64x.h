@@ -318,7 +318,8 @@ typedef struct b64x_strict_result {
  * for the E characters a text of that length holds (step 1 without the pad
  * rules; a length no text has counts the characters of its whole lines).
  * fmt NULL: plain.  Never more than b64x_decoded_cap(nchars); 0 for a fmt
- * with line_len == 0 or sep_len outside 1..4. */
+ * with line_len == 0, sep_len outside 1..4 or line_len + sep_len past
+ * 2^32 - 1 (no call accepts such a fmt). */
 uint64_t b64x_strict_decoded_cap(uint64_t nchars, const b64x_lines *fmt);
 
 /* Strictly decode the nchars bytes at d_in (fmt NULL: plain text) into d_out

@@ -40,6 +40,7 @@ KERNEL_SRC = async_amd/csrc/b64x_kernels.hip
 WRAP_SRC   = async_amd/csrc/b64x_wrap.hip
 STRICT_SRC = async_amd/csrc/b64x_strict.hip
 BATCH_SRC  = async_amd/csrc/b64x_lines_batch.hip
+SKIP_SRC   = async_amd/csrc/b64x_skip.hip
 # Every header the line-wrapped encode, the strict decode and their ragged
 # forms include: the plan arithmetic, the common device header and the
 # per-lane bodies the one-buffer and the ragged-batch units share.
@@ -80,19 +81,23 @@ $(OBJDIR)/b64x_strict.o: $(STRICT_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 $(OBJDIR)/b64x_lines_batch.o: $(BATCH_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# The strict decode that skips line breaks: likewise, linked after all four.
+$(OBJDIR)/b64x_skip.o: $(SKIP_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
 $(OBJDIR)/b64x_kernels_hooks.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_check.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DB64X_TEST_HOOKS -c $< -o $@
 
-$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o
+$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libb64x_hooks.so
 
-$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(HOST_OBJ)
+$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64.so
 
-$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
+$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64_core.so
 
 $(ORACLE): oracle/b64_oracle.c oracle/b64_oracle.h

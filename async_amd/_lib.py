@@ -74,6 +74,16 @@ class Lines(ctypes.Structure):
 LINES_TRAILING = 1  # B64X_LINES_TRAILING
 
 
+class Skip(ctypes.Structure):
+    """b64x_skip: the first n (0..8) of `bytes` are skipped wherever they
+    stand (b64x_decode_strict_skip_*)."""
+
+    _fields_ = [
+        ("n", ctypes.c_uint32),
+        ("bytes", ctypes.c_uint8 * 8),
+    ]
+
+
 class StrictResult(ctypes.Structure):
     """b64x_strict_result, 24 bytes, written by the device: the bytes decoded,
     or the kind (STRICT_*) and text offset of the first offence."""
@@ -91,6 +101,7 @@ STRICT_OK, STRICT_CHAR, STRICT_SEP, STRICT_PAD, STRICT_BITS, STRICT_LENGTH = ran
 STRICT_NAMES = ("ok", "char", "sep", "pad", "bits", "length")
 
 assert ctypes.sizeof(Lines) == 16
+assert ctypes.sizeof(Skip) == 12
 assert ctypes.sizeof(DecResult) == 40
 assert ctypes.sizeof(StrictResult) == 24
 STRICT_RES_BYTES = ctypes.sizeof(StrictResult)
@@ -102,6 +113,7 @@ _vp = ctypes.c_void_p
 _int = ctypes.c_int
 _ap = ctypes.POINTER(Alphabet)
 _lp = ctypes.POINTER(Lines)
+_sp = ctypes.POINTER(Skip)
 
 # name -> (restype, argtypes); every symbol include/b64x.h declares.
 SIGNATURES = {
@@ -125,6 +137,9 @@ SIGNATURES = {
     "b64x_decode_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _vp]),
     "b64x_encode_lines_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _ap, _lp, _vp]),
     "b64x_decode_strict_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _lp, _vp]),
+    "b64x_strict_skip_workspace_size": (_u64, [_u64, ctypes.c_bool]),
+    "b64x_decode_strict_skip_dev": (_int, [_vp, _u64, _vp, _vp, _ap, _sp, _vp, _vp]),
+    "b64x_decode_strict_skip_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _sp, _vp, _vp]),
     "b64x_session_open": (_vp, [_u64]),
     "b64x_session_close": (None, [_vp]),
     "b64x_session_acquire": (_vp, [_u64]),
@@ -234,6 +249,14 @@ def lines(line_len: int = 76, sep: bytes = b"\r\n", trailing: bool = True) -> Li
         raise ValueError("line_len out of range")
     return Lines(line_len, len(sep), (ctypes.c_uint8 * 4)(*sep),
                  LINES_TRAILING if trailing else 0)
+
+
+def skip_set(skip: bytes = b"\r\n") -> Skip:
+    """Build a b64x_skip; the library validates it against the alphabet (-EINVAL)."""
+    skip = bytes(skip)
+    if len(skip) > 8:
+        raise ValueError("the skip set is at most 8 bytes")
+    return Skip(len(skip), (ctypes.c_uint8 * 8)(*skip))
 
 
 def alphabet(pos62=-1, pos63=-1, pad=True, padchar=-1) -> Alphabet:

@@ -24,6 +24,12 @@ buffers and batches instead of a pull-model stream:
                                per buffer     (b64x_decode_strict_batch)
     lines_batch_layout / strict_batch_layout   their output offsets, from the
                                input offsets, on the tensor's own device
+    decode_strict_skip(x)      one buffer, strict, ignoring CR and LF (or another
+                               small set of bytes) wherever they stand; also
+                               validate-only   (b64x_decode_strict_skip_dev)
+    decode_strict_skip_batch                   ragged batches of it, one record
+                               per buffer      (b64x_decode_strict_skip_batch)
+    skip_batch_layout                          its output offsets
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
 missing or a call fails; nothing here computes base64 on the CPU.
@@ -484,6 +490,102 @@ def decode_strict_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor
         _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf,
         _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), _ptr(result),
         ctypes.byref(a), ref, _stream(stream)))
+
+
+def strict_skip_workspace_size(nchars: int, validate_only: bool = False) -> int:
+    """Workspace bytes decode_strict_skip() needs for nchars bytes of text."""
+    return int(_lib.load().b64x_strict_skip_workspace_size(nchars, validate_only))
+
+
+def decode_strict_skip(x: torch.Tensor, skip: bytes = b"\r\n", out: torch.Tensor | None = None,
+                       validate_only: bool = False, abc=None,
+                       workspace: torch.Tensor | None = None,
+                       result: torch.Tensor | None = None, stream=None) -> StrictDecoded:
+    """Strictly decode a device buffer of base64 text, ignoring the bytes of
+    `skip` wherever they stand (the default: CR and LF): accepts exactly the
+    texts whose other bytes decode_strict() accepts as plain text, with the
+    same bytes; any other text is refused, the record naming the kind and the
+    offset of the first offence.  validate_only: the text is read once and
+    only the record is written (`out` stays as it is, or is an empty tensor).
+    workspace: strict_skip_workspace_size(len, validate_only) bytes, zeroed
+    before their first use; allocated and zeroed here when None."""
+    lib = _lib.load()
+    a = _abc(abc)
+    k = _lib.skip_set(skip)
+    _u8(x, "input")
+    n = x.numel()
+    if validate_only:
+        if out is None:
+            out = torch.empty(0, dtype=torch.uint8, device=x.device)
+    else:
+        cap = decoded_cap(n)
+        if out is None:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=x.device)
+        _u8(out, "output")
+        if out.numel() < cap:
+            raise ValueError("output too small")
+    if result is None:
+        result = torch.empty(STRICT_RES_BYTES, dtype=torch.uint8, device=x.device)
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES:
+        raise ValueError("result too small")
+    # an empty text needs the head alone (a length of 0 asks the lenient
+    # decoder's size function for its largest workspace)
+    need = strict_skip_workspace_size(n, validate_only or n == 0)
+    if workspace is None:
+        workspace = torch.zeros(need, dtype=torch.uint8, device=x.device)
+    _u8(workspace, "workspace")
+    if workspace.numel() < need:
+        raise ValueError("workspace too small")
+    s = stream if stream is not None else torch.cuda.current_stream()
+    # an empty tensor has no address; nothing is read or written through the stand-in
+    _lib.check("b64x_decode_strict_skip_dev", lib.b64x_decode_strict_skip_dev(
+        _ptr(x) if n else _ptr(result),
+        n, None if validate_only else (_ptr(out) if out.numel() else _ptr(result)),
+        _ptr(result), ctypes.byref(a), ctypes.byref(k), _ptr(workspace), s.cuda_stream))
+    return StrictDecoded(out, result, s)
+
+
+def skip_batch_layout(in_off: torch.Tensor, align: int = 4) -> torch.Tensor:
+    """Output offsets for decode_strict_skip_batch(): nbuf + 1 int64 entries,
+    entry i the start of text i's decode capacity (decoded_cap of its length,
+    the start rounded up to `align`), the last the size of the arena.  Like
+    lines_batch_layout(), tensor ops on in_off's own device."""
+    return _starts((_lengths(in_off) + 3) // 4 * 3, align)
+
+
+def decode_strict_skip_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor | None,
+                             out_off: torch.Tensor | None, result: torch.Tensor,
+                             skip: bytes = b"\r\n", abc=None,
+                             workspace: torch.Tensor | None = None, stream=None) -> None:
+    """Ragged batch of decode_strict_skip(): text i = x[in_off[i]:in_off[i+1]]
+    is judged on its own, its b64x_strict_result in bytes [24 i, 24 i + 24) of
+    `result`, and decoded into out[out_off[i]:] (skip_batch_layout() gives the
+    offsets).  out None: validate only (out_off and workspace are not used).
+    workspace: 8 bytes per buffer, allocated here when None.  Replays on other
+    lengths like decode_strict_batch()."""
+    lib = _lib.load()
+    a = _abc(abc)
+    k = _lib.skip_set(skip)
+    nbuf = in_off.numel() - 1
+    _offsets(in_off, nbuf + 1, "in_off")
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES * nbuf:
+        raise ValueError("result must hold 24 bytes per buffer")
+    _u8(x, "input")
+    if out is not None:
+        _u8(out, "output")
+        _offsets(out_off, nbuf, "out_off")
+        if workspace is None:
+            workspace = torch.empty(8 * max(nbuf, 1), dtype=torch.uint8, device=x.device)
+        _u8(workspace, "workspace")
+        if workspace.numel() < 8 * nbuf:
+            raise ValueError("workspace must hold 8 bytes per buffer")
+    _lib.check("b64x_decode_strict_skip_batch", lib.b64x_decode_strict_skip_batch(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf,
+        None if out is None else (_ptr(out) if out.numel() else _ptr(in_off)),
+        None if out is None else _ptr(out_off), _ptr(result), ctypes.byref(a), ctypes.byref(k),
+        None if out is None else _ptr(workspace), _stream(stream)))
 
 
 def release_stream(stream=None) -> None:

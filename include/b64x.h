@@ -400,6 +400,108 @@ int b64x_decode_strict_batch(const void *d_in, const uint64_t *d_in_off, uint32_
                              const b64x_alphabet *abc, const b64x_lines *fmt /* NULL: plain */,
                              void *stream);
 
+/* ---- strict decode that skips line breaks ------------------------------ */
+
+/* What `base64 -d`, a PEM reader or a mail library does lies between the
+ * lenient decoder (every stranger skipped, nothing reported) and
+ * b64x_decode_strict_* (one exact line format): a small, named set of bytes
+ * -- CR and LF, perhaps space and tab -- is ignored wherever it stands,
+ * anything else is refused, and the caller learns where the first offence is.
+ * Added within ABI 7 (symbols only).
+ *
+ * `abc` is read as the strict decoder reads it ((char) -1 gives the
+ * defaults; pad and padchar are honoured).  The record is b64x_strict_result;
+ * B64X_STRICT_SEP is never reported.  The result for any text t[0..n) is what
+ * this scalar procedure returns:
+ *  1. Kept bytes.  u is the bytes of t that are not in the skip set, in
+ *     order; kept byte e stands at offset o(e) of t.  E = |u|.
+ *  2. Pads: step 3 of the strict procedure on u.  With pad, npad = 0 unless
+ *     u[E-1] is the pad character; then 2 if u[E-2] is too, else 1.  Without
+ *     pad, 0.  D = E - npad.  Skipped bytes may stand between the pads and
+ *     after them.
+ *  3. Offences at a byte.  A kept byte e < D that is the pad character (with
+ *     pad) is PAD, else one outside the 64 is CHAR.  The record holds the
+ *     kind and the offset o(e) of the offence at the lowest offset.  Unlike
+ *     the strict calls, these come before LENGTH: the text has to be read to
+ *     know E anyway, and the caller wants the position of the junk byte.
+ *  4. Length.  No offence so far: {LENGTH, err_pos = n} if pad and
+ *     E mod 4 != 0, or not pad and E mod 4 == 1.
+ *  5. Unused bits.  None so far: BITS at o(D-1), as in strict step 4.
+ *  6. Accepted: out_len = 3 floor(D/4) + (0, -, 1, 2)[D mod 4] and the bytes
+ *     are those of the D sextets.  E == 0 (n == 0, or skipped bytes only) is
+ *     accepted with out_len 0 and still writes the record.  With an offence,
+ *     out_len = 0 and the output bytes are unspecified.
+ * Consequence: the call accepts t if and only if b64x_decode_strict_dev(u,
+ * plain) accepts u, and then with the same bytes.
+ *
+ * The bytes come from the lenient decoder on the caller's workspace: a
+ * decoding call enqueues b64x_decode_dev (the batch: b64x_decode_batch) on
+ * the same text, whose output for an accepted text is by definition these
+ * bytes.  The verdict is a read-only pass of its own over the text and a
+ * finish step; with d_out NULL only those run (validate only: the text is
+ * read once and nothing but the record and the workspace head is written). */
+typedef struct b64x_skip {
+    uint32_t n;        /* 0..8 */
+    uint8_t bytes[8];  /* the first n are skipped; duplicates are fine */
+} b64x_skip;           /* NULL: {2, "\r\n"} */
+
+/* Device workspace bytes of b64x_decode_strict_skip_dev: a fixed head (a
+ * b64x_dec_result for the lenient decoder and a slot per block of the
+ * checking pass), then, unless validate_only, b64x_decode_workspace_size(
+ * nchars) bytes for the lenient decoder. */
+uint64_t b64x_strict_skip_workspace_size(uint64_t nchars, bool validate_only);
+
+/* Judge the nchars bytes at d_in as above and, with d_out not NULL, decode
+ * them into d_out (capacity b64x_decoded_cap(nchars)); *d_res (device memory,
+ * 8-byte aligned) receives the record, written whole by the call.
+ * d_workspace: b64x_strict_skip_workspace_size(nchars, d_out == NULL) bytes
+ * of device memory, 8-byte aligned.  The head needs no preparation.  The part
+ * behind it is b64x_decode_dev's d_workspace and inherits its rules: zero
+ * before its first use, one per stream; the lenient decoder's held models and
+ * hints work on it as they do there, and none of them decides a byte.
+ * Checked in this order: a NULL d_in, d_res or d_workspace (or a record or
+ * workspace not 8-byte aligned) is -EINVAL -- d_out may be NULL, and
+ * nchars == 0 still wants a d_in; a skip set with n > 8, or with a byte that
+ * is one of the 64 characters under abc or (with pad) the pad character, is
+ * -EINVAL; the alphabet rules of b64x_decode_strict_dev; then -ENODEV without
+ * a gfx950 device.
+ * Asynchronous and capture-safe: nothing is allocated or synchronised and no
+ * library workspace is taken; the caller's workspace is the only scratch.
+ * The record is deterministic whichever wave sees an offence.  Nothing outside
+ * [d_in, d_in + nchars) is read, the wide loads at the head and tail of an
+ * unaligned text included; nothing outside the output capacity, the record
+ * and the workspace is written.  Any alignment of the text and the output is
+ * accepted; no 32-bit limit on nchars.  The finish step walks back from the
+ * end of the text to its last three kept bytes 1,024 bytes at a time in one
+ * wave: a text that ends in a very long run of skipped bytes is exact but is
+ * walked at that one wave's rate. */
+int b64x_decode_strict_skip_dev(const void *d_in, uint64_t nchars,
+                                void *d_out /* NULL: validate only */, b64x_strict_result *d_res,
+                                const b64x_alphabet *abc, const b64x_skip *skip,
+                                void *d_workspace, void *stream);
+
+/* Ragged batch, addressed as b64x_decode_strict_batch: text i is judged on
+ * its own, err_pos an offset inside the buffer, its bytes (d_out not NULL)
+ * at d_out + d_out_off[i] with capacity b64x_decoded_cap(len_i).  Lengths are
+ * read on the device: the checking kernel's grid and arguments depend on
+ * nbuf, abc and skip only.  One wave judges one buffer, in passes of 1,024
+ * bytes, and writes its record whole; a buffer of hundreds of MiB is exact but
+ * runs at one wave's rate and belongs on the one-buffer call.  With d_out not
+ * NULL the bytes come from b64x_decode_batch on the same offsets, its
+ * d_outlen being d_workspace (8 nbuf bytes, 8-byte aligned); the record's
+ * out_len is the checking kernel's own, 0 on an offence.
+ * Checked in this order: nbuf == 0 returns 0; NULL d_in, d_in_off or d_res
+ * (or records not 8-byte aligned) -EINVAL, and with d_out not NULL a NULL
+ * d_out_off or d_workspace too (a validate-only batch needs neither); the
+ * skip set; the alphabet; then -ENODEV. */
+int b64x_decode_strict_skip_batch(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
+                                  void *d_out /* NULL: validate only */,
+                                  const uint64_t *d_out_off,
+                                  b64x_strict_result *d_res /* nbuf */,
+                                  const b64x_alphabet *abc, const b64x_skip *skip,
+                                  void *d_workspace /* 8*nbuf bytes; unused when d_out is NULL */,
+                                  void *stream);
+
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 
 typedef struct b64x_session b64x_session;

@@ -41,6 +41,9 @@ WRAP_SRC   = async_amd/csrc/b64x_wrap.hip
 STRICT_SRC = async_amd/csrc/b64x_strict.hip
 BATCH_SRC  = async_amd/csrc/b64x_lines_batch.hip
 SKIP_SRC   = async_amd/csrc/b64x_skip.hip
+ROWS_SRC   = async_amd/csrc/b64x_skip_rows.hip
+# What the two units of the strict decode that skips line breaks share.
+SKIP_HDRS  = async_amd/csrc/b64x_skip_body.h
 # Every header the line-wrapped encode, the strict decode and their ragged
 # forms include: the plan arithmetic, the common device header and the
 # per-lane bodies the one-buffer and the ragged-batch units share.
@@ -82,7 +85,11 @@ $(OBJDIR)/b64x_lines_batch.o: $(BATCH_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The strict decode that skips line breaks: likewise, linked after all four.
-$(OBJDIR)/b64x_skip.o: $(SKIP_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_skip.o: $(SKIP_SRC) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# Its one-pass form for strided rows: likewise, linked after all five.
+$(OBJDIR)/b64x_skip_rows.o: $(ROWS_SRC) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)
@@ -91,13 +98,13 @@ $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/
 $(OBJDIR)/b64x_kernels_hooks.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_check.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DB64X_TEST_HOOKS -c $< -o $@
 
-$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o
+$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libb64x_hooks.so
 
-$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(HOST_OBJ)
+$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64.so
 
-$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
+$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64_core.so
 
 $(ORACLE): oracle/b64_oracle.c oracle/b64_oracle.h

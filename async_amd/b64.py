@@ -30,6 +30,9 @@ buffers and batches instead of a pull-model stream:
     decode_strict_skip_batch                   ragged batches of it, one record
                                per buffer      (b64x_decode_strict_skip_batch)
     skip_batch_layout                          its output offsets
+    decode_strict_skip_strided                 uniform batches of it, each row read
+                               once by one kernel, no workspace; also
+                               validate-only   (b64x_decode_strict_skip_strided)
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
 missing or a call fails; nothing here computes base64 on the CPU.
@@ -586,6 +589,37 @@ def decode_strict_skip_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.T
         None if out is None else (_ptr(out) if out.numel() else _ptr(in_off)),
         None if out is None else _ptr(out_off), _ptr(result), ctypes.byref(a), ctypes.byref(k),
         None if out is None else _ptr(workspace), _stream(stream)))
+
+
+def decode_strict_skip_strided(x: torch.Tensor, in_stride: int, length: int, nbuf: int,
+                               out: torch.Tensor | None, out_stride: int, result: torch.Tensor,
+                               skip: bytes = b"\r\n", abc=None, stream=None) -> None:
+    """Uniform batch of decode_strict_skip(): row i (`length` bytes of text at
+    x + i*in_stride) is judged on its own, ignoring the bytes of `skip`
+    wherever they stand; its b64x_strict_result goes to bytes [24 i, 24 i + 24)
+    of `result`, and the bytes of an accepted row to out + i*out_stride
+    (decoded_cap(length) bytes of room each).  out None: validate only
+    (out_stride is not used).  One kernel that reads every row once; no
+    workspace."""
+    lib = _lib.load()
+    a = _abc(abc)
+    k = _lib.skip_set(skip)
+    _u8(x, "input")
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES * nbuf:
+        raise ValueError("result must hold 24 bytes per row")
+    if nbuf and x.numel() < (nbuf - 1) * in_stride + length:
+        raise ValueError("buffers too small for the batch")
+    if out is not None:
+        _u8(out, "output")
+        if nbuf and out.numel() < (nbuf - 1) * out_stride + decoded_cap(length):
+            raise ValueError("buffers too small for the batch")
+    # an empty tensor has no address; nothing is read or written through the stand-in
+    _lib.check("b64x_decode_strict_skip_strided", lib.b64x_decode_strict_skip_strided(
+        _ptr(x) if x.numel() else _ptr(result), in_stride, length, nbuf,
+        None if out is None else (_ptr(out) if out.numel() else _ptr(result)),
+        out_stride if out is not None else 0, _ptr(result),
+        ctypes.byref(a), ctypes.byref(k), _stream(stream)))
 
 
 def release_stream(stream=None) -> None:

@@ -15,8 +15,9 @@
 //       16-byte aligned *addresses*; a lane takes a chunk with one 16-byte
 //       load, a 256-lane block a tile of 4,096 bytes, the grid (CUs x 8
 //       blocks at most) strides over the tiles.  The first and the last chunk
-//       may reach outside the text: those are taken bytewise, the bytes
-//       outside never loaded.  A 256-entry LDS table gives each byte its
+//       may reach outside the text: those are taken in whole dwords where
+//       they lie inside it and bytewise for the rest, the bytes outside
+//       never loaded.  A 256-entry LDS table gives each byte its
 //       class as a packed count (kept / pad character / outside the 64), so a
 //       lane sums its 16 lookups and looks closer only where a pad character
 //       or a stranger showed.  Each lane keeps E (kept bytes), c (pad
@@ -33,15 +34,8 @@
 //       passes of 1,024 bytes, sums and minima in the wave's registers, the
 //       same backward walk, the record written whole.  No atomic at all.
 //
-// Why the first pad character decides PAD.  Let c be the number of pad
-// characters among the kept bytes u[0..E) and npad (0..2) the pads u ends in,
-// D = E - npad.  u[D..E) are pad characters by the definition of npad, so
-// exactly c - npad pad characters stand at kept positions below D: there is a
-// PAD offence iff c > npad.  If there is one, the first pad character of the
-// text stands below D too -- were it at or above D, every pad character would
-// be, and c would equal npad.  So the PAD offence at the lowest offset is the
-// first pad character, exactly when c > npad, and the pass needs to keep
-// nothing about pads but c and that one offset.
+// The skip set, the class table, the chunks, a wave's totals and the verdict
+// arithmetic are b64x_skip_body.h's, shared with b64x_skip_rows.hip.
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
@@ -49,36 +43,12 @@
 #include <string.h>
 
 #include "b64x.h"
-#include "b64x_strict_body.h"
+#include "b64x_skip_body.h"
 
 namespace {
 
-constexpr uint32_t kSkipTH = lines_plan::kBlockLanes;        // lanes per block (the table's builders)
-constexpr uint32_t kSkipWaves = kSkipTH / lines_plan::kPassLanes;
-constexpr uint32_t kChunk = 16;                              // bytes per lane
 constexpr uint32_t kWalkStep = lines_plan::kPassUnits;       // bytes per backward step (one wave)
-constexpr uint32_t kSkipBlocksPerCU = 8;
 constexpr uint32_t kSkipMaxGrid = 2048;                      // slots in the workspace head
-constexpr uint64_t kNone = ~0ull;
-
-// A byte's class as a packed count: 16 of them sum without a carry between
-// the fields (each at most 16).
-constexpr uint32_t kKept = 1u;          // bits 0..4: not a skipped byte
-constexpr uint32_t kPadc = 1u << 5;     // bits 5..9: the pad character (with pad)
-constexpr uint32_t kStranger = 1u << 10;  // bits 10..14: kept, outside the 64, not the pad character
-
-struct SkipSet {
-    uint64_t bytes;  // byte i in bits [8 i, 8 i + 8)
-    uint32_t n;
-};
-
-// What a block, a wave or a lane knows of its part of the text.
-struct Slot {
-    uint64_t E;           // kept bytes
-    uint64_t c;           // pad characters among them
-    uint64_t first_char;  // lowest offset of a stranger (kNone: none)
-    uint64_t first_pad;   // lowest offset of a pad character (kNone: none)
-};
 
 // The workspace head: a b64x_dec_result for the lenient decoder, then a slot
 // per block of the largest grid.  A multiple of 256, so that the lenient
@@ -86,66 +56,7 @@ struct Slot {
 constexpr uint64_t kHeadRes = 64;
 constexpr uint64_t kHeadBytes = (kHeadRes + kSkipMaxGrid * sizeof(Slot) + 255) & ~255ull;
 
-static_assert(sizeof(b64x_dec_result) <= kHeadRes && sizeof(Slot) == 32, "the head's layout");
-
-typedef uint32_t u32x4a16 __attribute__((ext_vector_type(4), aligned(16)));
-
-HD bool in_skip(uint32_t b, const SkipSet &k)
-{
-    bool hit = false;
-    for (uint32_t i = 0; i < k.n; i++) hit |= ((uint32_t) (k.bytes >> (8 * i)) & 0xFFu) == b;
-    return hit;
-}
-
-HD uint32_t skip_class(uint32_t b, const Alpha &a, const SkipSet &k)
-{
-    if (in_skip(b, k)) return 0;
-    const uint32_t t = classify(b, a);
-    return t < 64 ? kKept : t == 0xC0u ? kKept | kPadc : kKept | kStranger;
-}
-
-DEV void build_class_table(uint16_t *tab, const Alpha &a, const SkipSet &k)
-{
-    tab[threadIdx.x] = (uint16_t) skip_class(threadIdx.x, a, k);  // kSkipTH == 256
-}
-
-// ---------------------------------------------------------------- chunks --
-
-// The 16 bytes at the 16-byte aligned address A, as far as they lie in the
-// text [lo, hi): bit i of `valid` says that byte i does.  A chunk inside the
-// text is one 16-byte load; one that reaches outside is taken bytewise and
-// the bytes outside are never loaded.
-struct Chunk {
-    uint32_t w[4];
-    uint32_t valid;
-};
-
-DEV Chunk load_chunk(uintptr_t A, uintptr_t lo, uintptr_t hi)
-{
-    Chunk ch;
-    if (A >= lo && A + kChunk <= hi) {
-        const u32x4a16 v = __builtin_nontemporal_load((const u32x4a16 *) A);
-        ch.w[0] = v.x;
-        ch.w[1] = v.y;
-        ch.w[2] = v.z;
-        ch.w[3] = v.w;
-        ch.valid = 0xFFFFu;
-        return ch;
-    }
-    ch.w[0] = ch.w[1] = ch.w[2] = ch.w[3] = 0;
-    ch.valid = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kChunk; i++) {
-        const uintptr_t p = A + i;
-        if (p >= lo && p < hi) {
-            ch.w[i >> 2] |= (uint32_t) *(const uint8_t *) p << (8 * (i & 3));
-            ch.valid |= 1u << i;
-        }
-    }
-    return ch;
-}
-
-DEV uint32_t chunk_byte(const Chunk &ch, uint32_t i) { return (ch.w[i >> 2] >> (8 * (i & 3))) & 0xFFu; }
+static_assert(sizeof(b64x_dec_result) <= kHeadRes, "the head's layout");
 
 // One chunk into a lane's slot; off0: the text offset of the chunk's byte 0
 // (wraps below zero for a first chunk that starts before the text, and the
@@ -178,28 +89,6 @@ DEV void scan_chunk(const uint16_t *tab, const Chunk &ch, uint64_t off0, Slot *s
     if (fp < s->first_pad) s->first_pad = fp;
 }
 
-// The chunks of a text: from the 16-byte aligned address at or below its
-// first byte to the one that holds its last.
-DEV uint64_t chunk_count(uintptr_t lo, uint64_t n)
-{
-    return n ? ((lo + n + kChunk - 1) >> 4) - (lo >> 4) : 0;
-}
-
-// Every lane of the wave leaves with the wave's totals.
-DEV Slot wave_fold(Slot s)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < lines_plan::kPassLanes; d <<= 1) {
-        s.E += __shfl_xor((unsigned long long) s.E, d);
-        s.c += __shfl_xor((unsigned long long) s.c, d);
-        const uint64_t fc = __shfl_xor((unsigned long long) s.first_char, d);
-        const uint64_t fp = __shfl_xor((unsigned long long) s.first_pad, d);
-        if (fc < s.first_char) s.first_char = fc;
-        if (fp < s.first_pad) s.first_pad = fp;
-    }
-    return s;
-}
-
 // ---------------------------------------------------------- the verdict --
 
 // The last `want` (<= 3, <= E) kept bytes of the text, the last one first,
@@ -208,11 +97,6 @@ DEV Slot wave_fold(Slot s)
 // step the ballot of the lanes that still hold a kept byte names the highest
 // one.  A text that ends in a long run of skipped bytes is walked at this one
 // wave's rate.
-struct Last3 {
-    uint32_t byte[3];
-    uint64_t off[3];
-};
-
 DEV Last3 last_kept(uintptr_t lo, uintptr_t hi, uint32_t lane, uint32_t want, const SkipSet &k)
 {
     Last3 r = {};
@@ -253,39 +137,9 @@ DEV Last3 last_kept(uintptr_t lo, uintptr_t hi, uint32_t lane, uint32_t want, co
 DEV b64x_strict_result wave_verdict(const uint8_t *in, uint64_t n, const Slot &s, uint32_t lane,
                                     const Alpha &a, const SkipSet &k)
 {
-    b64x_strict_result r;
-    r.out_len = 0;
-    r.err_pos = 0;
-    r.err = B64X_STRICT_OK;
-    r.reserved = 0;
-    if (s.E == 0) return r;
-    const Last3 l = last_kept((uintptr_t) in, (uintptr_t) in + n, lane, s.E < 3 ? (uint32_t) s.E : 3u, k);
-    uint32_t npad = 0;
-    if (a.pad && l.byte[0] == a.padc) npad = (s.E >= 2 && l.byte[1] == a.padc) ? 2 : 1;
-    const uint64_t D = s.E - npad;
-    const bool pad_offence = s.c > npad;  // then first_pad is it (the unit's header)
-    if (pad_offence && s.first_pad < s.first_char) {
-        r.err = B64X_STRICT_PAD;
-        r.err_pos = s.first_pad;
-    } else if (s.first_char != kNone) {
-        r.err = B64X_STRICT_CHAR;
-        r.err_pos = s.first_char;
-    } else if (a.pad ? (s.E & 3) != 0 : (s.E & 3) == 1) {
-        r.err = B64X_STRICT_LENGTH;
-        r.err_pos = n;
-    } else {
-        const uint32_t r4 = (uint32_t) D & 3u;
-        // u[D - 1] is the kept byte npad places from the end, one of the 64
-        const uint32_t b = npad == 0 ? l.byte[0] : npad == 1 ? l.byte[1] : l.byte[2];
-        const uint64_t off = npad == 0 ? l.off[0] : npad == 1 ? l.off[1] : l.off[2];
-        if (D > 0 && r4 >= 2 && (classify(b, a) & (r4 == 2 ? 15u : 3u))) {
-            r.err = B64X_STRICT_BITS;
-            r.err_pos = off;
-        } else {
-            r.out_len = decoded_len(D);
-        }
-    }
-    return r;
+    if (s.E == 0) return skip_verdict(n, s, Last3{}, a);
+    return skip_verdict(
+        n, s, last_kept((uintptr_t) in, (uintptr_t) in + n, lane, s.E < 3 ? (uint32_t) s.E : 3u, k), a);
 }
 
 // ------------------------------------------------------------- kernels --
@@ -390,39 +244,6 @@ __global__ __launch_bounds__(kSkipTH) void k_skip_check_batch(
         if (lane == 0) res[b] = r;
     }
 }
-
-// ---------------------------------------------------------------- host --
-
-// NULL: CR and LF.  The set's rules, in the order b64x.h states them.
-bool make_skip(const b64x_skip *skip, const Alpha &a, SkipSet *k)
-{
-    static const b64x_skip crlf = {2, {'\r', '\n', 0, 0, 0, 0, 0, 0}};
-    if (!skip) skip = &crlf;
-    if (skip->n > 8) return false;
-    k->bytes = 0;
-    k->n = skip->n;
-    for (uint32_t i = 0; i < skip->n; i++) {
-        const uint32_t t = classify(skip->bytes[i], a);
-        if (t < 64 || t == 0xC0u) return false;  // one of the 64, or the pad character (with pad)
-        k->bytes |= (uint64_t) skip->bytes[i] << (8 * i);
-    }
-    return true;
-}
-
-int device_cus(uint32_t *cus)
-{
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0) {
-        const int rc = hip_status();
-        return rc ? rc : -ENODEV;
-    }
-    *cus = (uint32_t) n;
-    return 0;
-}
-
-uint64_t at_most(uint64_t want, uint64_t cap) { return want < cap ? want : cap; }
 
 }  // namespace
 

@@ -502,6 +502,42 @@ int b64x_decode_strict_skip_batch(const void *d_in, const uint64_t *d_in_off, ui
                                   void *d_workspace /* 8*nbuf bytes; unused when d_out is NULL */,
                                   void *stream);
 
+/* Uniform rows, addressed as b64x_decode_strict_strided: row i is the `len`
+ * bytes at d_in + i*in_stride, judged on its own by the scalar procedure above
+ * (steps 1 to 6); its record goes to d_res[i], err_pos an offset in the row.
+ * `abc` is read as the strict decoder reads it, skip NULL means CR and LF,
+ * B64X_STRICT_SEP is never reported.  With d_out not NULL an accepted row's
+ * out_len bytes go to d_out + i*out_stride (capacity b64x_decoded_cap(len));
+ * with an offence out_len is 0 and the row's output bytes are unspecified.
+ * len == 0 is valid: every record is {0, 0, OK}.  Added within ABI 7 (a
+ * symbol only).
+ * One pass, one kernel: the wave that owns a row reads its text once, in
+ * passes of 1,024 bytes, compacts the kept characters and decodes them
+ * itself, and writes the record whole (the caller need not zero the records).
+ * Unlike the two calls above there is no workspace and the lenient decoder
+ * takes no part.  For row i nothing is written outside [d_out + i*out_stride,
+ * + b64x_decoded_cap(len)) and the records, and nothing is read outside the
+ * row's len bytes, the wide loads at an unaligned row's head and tail
+ * included.  Input and output must not overlap.  Any alignment of the base
+ * addresses and of the strides is accepted; rows whose input and output
+ * addresses are both 4-byte aligned are the fast shape.  No 32-bit limit on
+ * len, the strides or i*stride -- but one wave walks one row, so a row of
+ * hundreds of MiB, exact as it is, runs at one wave's rate (the kernel
+ * balances a batch over rows, not over the bytes of one): such a text belongs
+ * on b64x_decode_strict_skip_dev.
+ * Asynchronous, capture-safe and exact: no workspace, no allocation, no
+ * synchronisation, no library state, no hint; no memset node and no global
+ * atomic.
+ * Checked in this order: nbuf == 0 returns 0; a NULL d_in or d_res (or records
+ * not 8-byte aligned) -EINVAL; in_stride < len -EINVAL; with d_out not NULL,
+ * out_stride < b64x_decoded_cap(len) -EINVAL; the skip-set rules of
+ * b64x_decode_strict_skip_dev; the alphabet rules of b64x_decode_strict_dev;
+ * then -ENODEV without a gfx950 device. */
+int b64x_decode_strict_skip_strided(const void *d_in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                                    void *d_out /* NULL: validate only */, uint64_t out_stride,
+                                    b64x_strict_result *d_res /* nbuf */,
+                                    const b64x_alphabet *abc, const b64x_skip *skip, void *stream);
+
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 
 typedef struct b64x_session b64x_session;

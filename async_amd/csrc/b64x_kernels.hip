@@ -449,8 +449,26 @@ DEV u32x3a4 ld12(const uint8_t *p)
 // (profiles/r03_ab_enc*.jsonl); the alphabet read across lanes by
 // ds_bpermute 445 us; two quads per lane 405; 512- and 1,024-lane blocks
 // +20 / +120 us; software pipelining and cached loads slower (r01_v6_*).
+//
+// The last kEncPlainTiles whole tiles (256 MiB of characters, the size of
+// the memory-side cache) of a buffer longer than that are stored with the
+// plain policy: those lines stay in that cache, and a reader of the
+// characters that runs next -- k_decode_lines, whose non-temporal loads hit
+// there -- takes them from it.  Front to back on both sides: non-temporal
+// traffic does not displace the lines, so which end the reader starts at
+// does not matter; plain loads on the reader's side do displace them and
+// lose.  Measured on distinct buffers taken in turn, so that
+// no encode overwrites lines still dirty in the cache
+// (scripts/ab_pair.py, profiles/r07_pair_final4.jsonl): the 1 GiB encode and
+// the decode of its characters 782.7 -> 768.2 us.  The price: the window is
+// written back later, so the encode alone is 390.3 -> 393.0 us and an encode
+// followed by a kernel that does not read its characters 782.7 -> 786.5.
+// A buffer no longer than the window keeps every store non-temporal (stored
+// plain throughout, the 16 MiB encode ran 7.6 -> 8.3 us,
+// r07_pair_small_plain.jsonl; those are the sizes the stages use).  Both
+// policies' loops are unguarded and unmasked.
 constexpr uint32_t kEncTH = 256;
-
+constexpr uint64_t kEncPlainTiles = ((uint64_t) 256 << 20) / (16 * kEncTH);
 
 __global__ __launch_bounds__(kEncTH) void k_encode_flat(
     const uint8_t *__restrict__ in, uint8_t *__restrict__ out, uint64_t full, uint64_t n,
@@ -462,10 +480,22 @@ __global__ __launch_bounds__(kEncTH) void k_encode_flat(
     const uint32_t tid = threadIdx.x;
     build_enc_table(tab, a);
     block_sync();
-    for (uint64_t t = blockIdx.x; t < full; t += gridDim.x) {
+    // The first plain tile (none where the buffer is no longer than the
+    // window).  Two loops, not one loop with a branch: the first is the
+    // loop this kernel always had, to another bound, and is all that runs
+    // for a buffer without a window; and two stores in the arms of one branch
+    // the compiler merges into one store without the nt bit.
+    const uint64_t plain_from = full > kEncPlainTiles ? full - kEncPlainTiles : full;
+    uint64_t t = blockIdx.x;
+    for (; t < plain_from; t += gridDim.x) {
         const uint64_t q = t * kEncTH + tid;
         const u32x3a4 v = ld12<true>(in + q * 12);
         store16<true>(out + q * 16, enc_quad(tab, v.x, v.y, v.z));
+    }
+    for (; t < full; t += gridDim.x) {
+        const uint64_t q = t * kEncTH + tid;
+        const u32x3a4 v = ld12<true>(in + q * 12);
+        store16<false>(out + q * 16, enc_quad(tab, v.x, v.y, v.z));
     }
     if (blockIdx.x == gridDim.x - 1) {
         const uint64_t nq = n / 12;

@@ -4267,6 +4267,67 @@ int occupancy_of(K kernel)
 // profiles/r01_v6_*).
 constexpr auto k_pass1 = k_decode_pass1<2, true>;
 
+// Output slots per lane of k_encode_tight2 (1: +9 %, 4: +5 % on config 4,
+// profiles/r05_ab_tight_shapes.jsonl).
+constexpr int kTightU = 2;
+
+// Which kernel b64x_encode_dev / b64x_encode_strided launch.
+enum EncPath : int {
+    kEncNothing = 0,  // nothing to encode: no launch
+    kEncFlat = 1,     // k_encode_flat: one dword-aligned buffer
+    kEncGeneric = 2,  // k_encode: one misaligned buffer
+    kEncTight2 = 3,   // k_encode_tight2: tight rows, one launch
+    kEncStrided = 4,  // k_encode_strided: any other uniform batch
+};
+
+struct EncChoice {
+    int path;            // an EncPath, or -EINVAL
+    uint32_t magic;      // kEncTight2: ceil(2^32 / E)
+    uint64_t rel_bound;  // kEncTight2: the kernel's `rel` stays below this
+};
+
+// The launchers' decision, from the addresses and the shape alone (host
+// arithmetic, no HIP call).  b64x_encode_dev passes nbuf = 1, which ignores
+// the strides.
+EncChoice encode_choice(uintptr_t in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                        uintptr_t out, uint64_t out_stride, bool pad)
+{
+    EncChoice c = {kEncNothing, 0, 0};
+    if (nbuf == 0 || len == 0) return c;
+    c.path = -EINVAL;
+    if (!in || !out) return c;
+    if (nbuf == 1) {
+        // Misaligned buffers: the generic slot kernel (bytewise where needed).
+        c.path = ((in | out) & 3) == 0 ? kEncFlat : kEncGeneric;
+        return c;
+    }
+    const uint64_t E = b64x_encoded_len(len, pad);
+    if (in_stride < len || out_stride < E) return c;
+    const uint64_t slots = (len + 11) / 12 * nbuf;
+    if (slots > 0xFFFFFFFFull - 4096) return c;
+    // Any layout but the tight one: one lane per (buffer, quad).
+    c.path = kEncStrided;
+    const uint32_t r = (uint32_t) (len % 3);
+    const bool tight = in_stride == len && out_stride == E && len >= 16 && (pad || r == 0) &&
+                       (in & 3) == 0 && (out & 15) == 0;
+    if (tight && E < (1u << 20)) {
+        // k_encode_tight2 splits rel < E + 16 * U * kThreads with a multiply-
+        // high by magic = (2^32 + e) / E: exact while rel * e < 2^32.
+        const uint32_t magic = (uint32_t) ((0xFFFFFFFFull + E) / E);
+        const uint64_t e = (uint64_t) magic * E - (1ull << 32);
+        const uint64_t bound = E + 16ull * kTightU * kThreads;
+        if (bound * e < (1ull << 32)) {
+            c.path = kEncTight2;
+            c.magic = magic;
+            c.rel_bound = bound;
+        }
+    }
+    return c;
+}
+
+// k_encode's grid is capped at the blocks the device holds at once.
+uint64_t encode_grid_cap(const DeviceInfo *d) { return (uint64_t) d->cus * d->enc_blocks_per_cu; }
+
 }  // namespace
 
 // ================================================================ C ABI ==
@@ -4379,79 +4440,74 @@ int b64x_bind_thread(int device)
     return node;
 }
 
+// The kernels behind both encode entry points, launched as encode_choice
+// decided.
+static int encode_launch(const EncChoice &c, const void *d_in, uint64_t in_stride, uint64_t len,
+                         uint32_t nbuf, void *d_out, uint64_t out_stride,
+                         const b64x_alphabet *abc, void *stream)
+{
+    if (c.path <= kEncNothing) return c.path;
+    const DeviceInfo *d = device_info();
+    if (!d) return -ENODEV;
+    const EncAlpha ea = enc_alpha(abc);
+    if (c.path == kEncFlat) {
+        const uint64_t tiles = len / 12 / kEncTH;
+        hipLaunchKernelGGL(k_encode_flat, dim3(cap_grid(tiles, (uint64_t) 1 << 31)),
+                           dim3(kEncTH), 0, (hipStream_t) stream, (const uint8_t *) d_in,
+                           (uint8_t *) d_out, tiles, len, ea);
+        return launch_status();
+    }
+    if (c.path == kEncGeneric) {
+        const uint64_t slots = (len + 11) / 12;
+        const uint64_t per_block = (uint64_t) kThreads * kEncUnroll;
+        uint32_t grid = cap_grid((slots + per_block - 1) / per_block, encode_grid_cap(d));
+        hipLaunchKernelGGL(k_encode, dim3(grid), dim3(kThreads), 0, (hipStream_t) stream,
+                           (const uint8_t *) d_in, (uint64_t) 0, len, 1u, (uint8_t *) d_out,
+                           (uint64_t) 0, slots, slots, ea);
+        return launch_status();
+    }
+    if (c.path == kEncTight2) {
+        constexpr int U = kTightU;
+        const uint64_t E = b64x_encoded_len(len, ea.pad);
+        const uint32_t r = (uint32_t) (len % 3);
+        const uint64_t total_out = (uint64_t) nbuf * E;
+        const uint64_t nslots = (total_out + 15) / 16;
+        const uint64_t tail_slot = (nbuf - 1) * E / 16 ? (nbuf - 1) * E / 16 - 1 : 0;
+        const uint64_t m64 = ~0ull / E + 1;
+        const uint64_t per = (uint64_t) U * kThreads;
+        const dim3 g((uint32_t) ((nslots + per - 1) / per));
+        hipLaunchKernelGGL(k_encode_tight2<U>, g, dim3(kThreads), 0, (hipStream_t) stream,
+                           (const uint8_t *) d_in, len, (uint32_t) E, r, c.magic, m64,
+                           (uint8_t *) d_out, nslots, (uint64_t) nbuf * len, total_out,
+                           tail_slot, ea);
+        return launch_status();
+    }
+    constexpr int US = 2;
+    const uint64_t qpb = (len + 11) / 12;
+    const uint64_t slots = qpb * nbuf;
+    const uint64_t per_block = (uint64_t) kThreads * US;
+    hipLaunchKernelGGL((k_encode_strided<US, true>), dim3((uint32_t) ((slots + per_block - 1) / per_block)),
+                       dim3(kThreads), 0, (hipStream_t) stream, (const uint8_t *) d_in,
+                       in_stride, len, nbuf, (uint8_t *) d_out, out_stride, (uint32_t) qpb,
+                       (uint32_t) slots, ea);
+    return launch_status();
+}
+
 int b64x_encode_dev(const void *d_in, uint64_t n, void *d_out,
                     const b64x_alphabet *abc, void *stream)
 {
-    if (n == 0) return 0;
-    if (!d_in || !d_out) return -EINVAL;
-    const DeviceInfo *d = device_info();
-    if (!d) return -ENODEV;
-    if (((((uintptr_t) d_in) | ((uintptr_t) d_out)) & 3) == 0) {
-        const uint64_t tiles = n / 12 / kEncTH;
-        hipLaunchKernelGGL(k_encode_flat, dim3(cap_grid(tiles, (uint64_t) 1 << 31)),
-                           dim3(kEncTH), 0, (hipStream_t) stream, (const uint8_t *) d_in,
-                           (uint8_t *) d_out, tiles, n, enc_alpha(abc));
-        return launch_status();
-    }
-    // Misaligned buffers: the generic slot kernel (bytewise where needed).
-    const uint64_t slots = (n + 11) / 12;
-    const uint64_t per_block = (uint64_t) kThreads * kEncUnroll;
-    uint32_t grid = cap_grid((slots + per_block - 1) / per_block,
-                             (uint64_t) d->cus * d->enc_blocks_per_cu);
-    hipLaunchKernelGGL(k_encode, dim3(grid), dim3(kThreads), 0, (hipStream_t) stream,
-                       (const uint8_t *) d_in, (uint64_t) 0, n, 1u, (uint8_t *) d_out,
-                       (uint64_t) 0, slots, slots, enc_alpha(abc));
-    return launch_status();
+    const EncChoice c = encode_choice((uintptr_t) d_in, n, n, 1, (uintptr_t) d_out, 0,
+                                      enc_alpha(abc).pad);
+    return encode_launch(c, d_in, n, n, 1, d_out, 0, abc, stream);
 }
 
 int b64x_encode_strided(const void *d_in, uint64_t in_stride, uint64_t len,
                         uint32_t nbuf, void *d_out, uint64_t out_stride,
                         const b64x_alphabet *abc, void *stream)
 {
-    if (nbuf == 0 || len == 0) return 0;
-    if (!d_in || !d_out) return -EINVAL;
-    if (nbuf == 1) return b64x_encode_dev(d_in, len, d_out, abc, stream);
-    if (in_stride < len || out_stride < b64x_encoded_len(len, enc_alpha(abc).pad))
-        return -EINVAL;
-    const uint64_t qpb = (len + 11) / 12;
-    const uint64_t slots = qpb * nbuf;
-    if (slots > 0xFFFFFFFFull - 4096) return -EINVAL;
-    const DeviceInfo *d = device_info();
-    if (!d) return -ENODEV;
-    // output slots per lane of k_encode_tight2 (1: +9 %, 4: +5 % on config
-    // 4, profiles/r05_ab_tight_shapes.jsonl)
-    constexpr int U = 2;
-    const EncAlpha ea = enc_alpha(abc);
-    const uint64_t E = b64x_encoded_len(len, ea.pad);
-    const uint32_t r = (uint32_t) (len % 3);
-    // Tight layout, one launch (k_encode_tight2).
-    const bool tight = in_stride == len && out_stride == E && len >= 16 && (ea.pad || r == 0) &&
-                       (((uintptr_t) d_in) & 3) == 0 && (((uintptr_t) d_out) & 15) == 0;
-    if (tight && E < (1u << 20)) {
-        const uint32_t magic = (uint32_t) ((0xFFFFFFFFull + E) / E);
-        const uint64_t e = (uint64_t) magic * E - (1ull << 32);
-        if ((E + 16ull * U * kThreads) * e < (1ull << 32)) {
-            const uint64_t total_out = (uint64_t) nbuf * E;
-            const uint64_t nslots = (total_out + 15) / 16;
-            const uint64_t tail_slot = (nbuf - 1) * E / 16 ? (nbuf - 1) * E / 16 - 1 : 0;
-            const uint64_t m64 = ~0ull / E + 1;
-            const uint64_t per = (uint64_t) U * kThreads;
-            const dim3 g((uint32_t) ((nslots + per - 1) / per));
-            hipLaunchKernelGGL(k_encode_tight2<U>, g, dim3(kThreads), 0, (hipStream_t) stream,
-                               (const uint8_t *) d_in, len, (uint32_t) E, r, magic, m64,
-                               (uint8_t *) d_out, nslots, (uint64_t) nbuf * len, total_out,
-                               tail_slot, ea);
-            return launch_status();
-        }
-    }
-    // Any other layout: one lane per (buffer, quad).
-    constexpr int US = 2;
-    const uint64_t per_block = (uint64_t) kThreads * US;
-    hipLaunchKernelGGL((k_encode_strided<US, true>), dim3((uint32_t) ((slots + per_block - 1) / per_block)),
-                       dim3(kThreads), 0, (hipStream_t) stream, (const uint8_t *) d_in,
-                       in_stride, len, nbuf, (uint8_t *) d_out, out_stride, (uint32_t) qpb,
-                       (uint32_t) slots, enc_alpha(abc));
-    return launch_status();
+    const EncChoice c = encode_choice((uintptr_t) d_in, in_stride, len, nbuf, (uintptr_t) d_out,
+                                      out_stride, enc_alpha(abc).pad);
+    return encode_launch(c, d_in, in_stride, len, nbuf, d_out, out_stride, abc, stream);
 }
 
 int b64x_encode_batch(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
@@ -5901,6 +5957,29 @@ uint64_t b64x__test_range_chunks(uint64_t chunks)
     const uint64_t old = g_test_range_chunks;
     g_test_range_chunks = chunks;
     return old;
+}
+// Test builds only: the path encode_choice takes for a call of
+// b64x_encode_strided (nbuf == 1: of b64x_encode_dev) with these addresses
+// and this shape -- 0 nothing, 1 k_encode_flat, 2 k_encode, 3
+// k_encode_tight2, 4 k_encode_strided, or -EINVAL -- and, for 3, the magic
+// it computed and the bound on `rel` its guard assumes.  No HIP call.
+int b64x__test_encode_path(uint64_t in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                           uint64_t out, uint64_t out_stride, int pad, uint32_t *magic,
+                           uint64_t *rel_bound)
+{
+    const EncChoice c = encode_choice((uintptr_t) in, in_stride, len, nbuf, (uintptr_t) out,
+                                      out_stride, pad != 0);
+    if (magic) *magic = c.magic;
+    if (rel_bound) *rel_bound = c.rel_bound;
+    return c.path;
+}
+
+// Test builds only: the block cap of k_encode's grid on the current device
+// (negative errno without one).
+int64_t b64x__test_encode_grid_cap(void)
+{
+    const DeviceInfo *d = device_info();
+    return d ? (int64_t) encode_grid_cap(d) : -ENODEV;
 }
 #endif
 

@@ -1,7 +1,8 @@
 # Build of the MI355X base64 byte-stream engine and its test oracle.
 #
 #   make            -> async_amd/libasync_b64.so  (product: HIP kernels + C ABI
-#                      + bytestream_1 stages + minimal loop/streams)
+#                      + host-only sessions/lanes unit + bytestream_1 stages
+#                      + minimal loop/streams)
 #                      oracle/liboracle.so          (test infrastructure only)
 #                      tests/csrc/libstage_harness.so, libstage_fake.so,
 #                      libb64x_hooks.so     (test infrastructure only)
@@ -25,6 +26,10 @@ ARCH     ?= gfx950
 # loading prologue for firmware without preload).
 HIPFLAGS  = --offload-arch=$(ARCH) -mcode-object-version=5 -O3 -std=c++17 -fPIC -Iasync_amd/csrc \
             -Wall -Wno-pass-failed -Iinclude -mllvm -amdgpu-kernarg-preload-count=16
+# The host-only C++ unit: the same language level and warnings, no offload
+# (as plain C++ hipcc does not add the HIP headers' directory itself).
+ROCM_PATH ?= /opt/rocm
+HOSTFLAGS = -O3 -std=c++17 -fPIC -Wall -Iasync_amd/csrc -Iinclude -isystem $(ROCM_PATH)/include
 CFLAGS    = -O2 -std=c11 -fPIC -Wall -Wextra -Wno-unused-parameter -Iinclude
 
 LIB      = async_amd/libasync_b64.so
@@ -37,6 +42,10 @@ HARNESS  = tests/csrc/libstage_harness.so
 OBJDIR   = build
 
 KERNEL_SRC = async_amd/csrc/b64x_kernels.hip
+# Host resource management (placement, sessions, lanes), and what it shares
+# with the kernel unit: the launchers it calls and the result check.
+SESSIONS_SRC = async_amd/csrc/b64x_sessions.cpp
+KERNEL_HDRS  = async_amd/csrc/b64x_launch.h async_amd/csrc/b64x_result_check.h
 WRAP_SRC   = async_amd/csrc/b64x_wrap.hip
 STRICT_SRC = async_amd/csrc/b64x_strict.hip
 BATCH_SRC  = async_amd/csrc/b64x_lines_batch.hip
@@ -55,6 +64,11 @@ HOST_SRC   = async_amd/csrc/fsalloc.c async_amd/csrc/loop.c async_amd/csrc/strea
 HEADERS    = $(wildcard include/*.h)
 
 HOST_OBJ   = $(patsubst async_amd/csrc/%.c,$(OBJDIR)/%.o,$(HOST_SRC))
+# The GPU side of every library next to its kernel object (b64x_kernels.o, or
+# the hooks build of it): the five satellite code objects, in link order,
+# and the host-only sessions unit.
+GPU_OBJ    = $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o \
+             $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(OBJDIR)/b64x_sessions.o
 
 # The same harness over the product's host C with a CPU stand-in for the GPU
 # side (tests/csrc/fake_b64x.c): deterministic, adversarially ordered tests
@@ -69,8 +83,12 @@ all: $(LIB) $(CORE) $(ORACLE) $(HARNESS) $(FAKE) $(HOOKS)
 $(OBJDIR):
 	mkdir -p $(OBJDIR)
 
-$(OBJDIR)/b64x_kernels.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_check.h | $(OBJDIR)
+$(OBJDIR)/b64x_kernels.o: $(KERNEL_SRC) $(HEADERS) $(KERNEL_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# Thread placement, sessions and batch lanes: host code only, no device pass.
+$(OBJDIR)/b64x_sessions.o: $(SESSIONS_SRC) $(HEADERS) $(KERNEL_HDRS) | $(OBJDIR)
+	$(HIPCC) -x c++ -D__HIP_PLATFORM_AMD__ $(HOSTFLAGS) -c $< -o $@
 
 # The line-wrapped encode: a code object of its own, linked after the kernels'.
 $(OBJDIR)/b64x_wrap.o: $(WRAP_SRC) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
@@ -95,16 +113,16 @@ $(OBJDIR)/b64x_skip_rows.o: $(ROWS_SRC) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | 
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(OBJDIR)/b64x_kernels_hooks.o: $(KERNEL_SRC) $(HEADERS) async_amd/csrc/b64x_result_check.h | $(OBJDIR)
+$(OBJDIR)/b64x_kernels_hooks.o: $(KERNEL_SRC) $(HEADERS) $(KERNEL_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DB64X_TEST_HOOKS -c $< -o $@
 
-$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o
+$(HOOKS): $(OBJDIR)/b64x_kernels_hooks.o $(GPU_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libb64x_hooks.so
 
-$(LIB): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(HOST_OBJ)
+$(LIB): $(OBJDIR)/b64x_kernels.o $(GPU_OBJ) $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64.so
 
-$(CORE): $(OBJDIR)/b64x_kernels.o $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
+$(CORE): $(OBJDIR)/b64x_kernels.o $(GPU_OBJ) $(OBJDIR)/b64_hub.o $(OBJDIR)/b64_stages.o $(OBJDIR)/b64_pin.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -Wl,-soname,libasync_b64_core.so
 
 $(ORACLE): oracle/b64_oracle.c oracle/b64_oracle.h

@@ -1,6 +1,6 @@
 /*
  * b64x_result_check.h -- internal: the host-side check of completion
- * records, shared by the library (b64x_kernels.hip) and the CPU test
+ * records, shared by the library (b64x_sessions.cpp, b64x_kernels.hip) and the CPU test
  * backend (tests/csrc/fake_b64x.c), so the deterministic stage tests run the
  * product's own check.
  *

@@ -51,8 +51,11 @@ STRICT_SRC = async_amd/csrc/b64x_strict.hip
 BATCH_SRC  = async_amd/csrc/b64x_lines_batch.hip
 SKIP_SRC   = async_amd/csrc/b64x_skip.hip
 ROWS_SRC   = async_amd/csrc/b64x_skip_rows.hip
-# What the two units of the strict decode that skips line breaks share.
+PIECES_SRC = async_amd/csrc/b64x_skip_pieces.hip
+# What the units of the strict decode that skips line breaks share, and the
+# walk of its two one-pass units.
 SKIP_HDRS  = async_amd/csrc/b64x_skip_body.h
+WALK_HDRS  = async_amd/csrc/b64x_skip_walk.h
 # Every header the line-wrapped encode, the strict decode and their ragged
 # forms include: the plan arithmetic, the common device header and the
 # per-lane bodies the one-buffer and the ragged-batch units share.
@@ -65,10 +68,11 @@ HEADERS    = $(wildcard include/*.h)
 
 HOST_OBJ   = $(patsubst async_amd/csrc/%.c,$(OBJDIR)/%.o,$(HOST_SRC))
 # The GPU side of every library next to its kernel object (b64x_kernels.o, or
-# the hooks build of it): the five satellite code objects, in link order,
+# the hooks build of it): the six satellite code objects, in link order,
 # and the host-only sessions unit.
 GPU_OBJ    = $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o \
-             $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(OBJDIR)/b64x_sessions.o
+             $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(OBJDIR)/b64x_skip_pieces.o \
+             $(OBJDIR)/b64x_sessions.o
 
 # The same harness over the product's host C with a CPU stand-in for the GPU
 # side (tests/csrc/fake_b64x.c): deterministic, adversarially ordered tests
@@ -107,7 +111,11 @@ $(OBJDIR)/b64x_skip.o: $(SKIP_SRC) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJ
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # Its one-pass form for strided rows: likewise, linked after all five.
-$(OBJDIR)/b64x_skip_rows.o: $(ROWS_SRC) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
+$(OBJDIR)/b64x_skip_rows.o: $(ROWS_SRC) $(WALK_HDRS) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# The same walk over texts that arrive in pieces: likewise, linked after all six.
+$(OBJDIR)/b64x_skip_pieces.o: $(PIECES_SRC) $(WALK_HDRS) $(SKIP_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)

@@ -106,6 +106,8 @@ assert ctypes.sizeof(DecResult) == 40
 assert ctypes.sizeof(StrictResult) == 24
 STRICT_RES_BYTES = ctypes.sizeof(StrictResult)
 RES_BYTES = ctypes.sizeof(DecResult)  # device buffers for one record
+SKIP_STATE_BYTES = 128  # B64X_SKIP_STATE_BYTES: a b64x_skip_state, all zero at the start of a text
+PIECE_FINAL = 1  # B64X_PIECE_FINAL
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -141,6 +143,9 @@ SIGNATURES = {
     "b64x_decode_strict_skip_dev": (_int, [_vp, _u64, _vp, _vp, _ap, _sp, _vp, _vp]),
     "b64x_decode_strict_skip_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _sp, _vp, _vp]),
     "b64x_decode_strict_skip_strided": (_int, [_vp, _u64, _u64, _u32, _vp, _u64, _vp, _ap, _sp, _vp]),
+    "b64x_skip_piece_cap": (_u64, [_u64]),
+    "b64x_decode_strict_skip_pieces": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _ap, _sp,
+                                              _vp]),
     "b64x_session_open": (_vp, [_u64]),
     "b64x_session_close": (None, [_vp]),
     "b64x_session_acquire": (_vp, [_u64]),

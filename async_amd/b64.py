@@ -33,6 +33,11 @@ buffers and batches instead of a pull-model stream:
     decode_strict_skip_strided                 uniform batches of it, each row read
                                once by one kernel, no workspace; also
                                validate-only   (b64x_decode_strict_skip_strided)
+    decode_strict_skip_pieces                  texts that arrive in pieces: many
+                               streams per call, each continued from a state
+                               in device memory (b64x_decode_strict_skip_pieces)
+    skip_states / skip_pieces_layout           its zeroed states and its output
+                               offsets; SKIP_STATE_BYTES, PIECE_FINAL
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
 missing or a call fails; nothing here computes base64 on the CPU.
@@ -45,8 +50,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import (RES_BYTES, STRICT_RES_BYTES, B64xError, DecResult,  # noqa: F401
-                   StrictResult, alphabet)
+from ._lib import (PIECE_FINAL, RES_BYTES, SKIP_STATE_BYTES, STRICT_RES_BYTES,  # noqa: F401
+                   B64xError, DecResult, StrictResult, alphabet)
 
 HOLD_TAIL = 1  # B64X_DEC_HOLD_TAIL
 EXPECT_JUNK = 2  # B64X_DEC_EXPECT_JUNK
@@ -620,6 +625,71 @@ def decode_strict_skip_strided(x: torch.Tensor, in_stride: int, length: int, nbu
         None if out is None else (_ptr(out) if out.numel() else _ptr(result)),
         out_stride if out is not None else 0, _ptr(result),
         ctypes.byref(a), ctypes.byref(k), _stream(stream)))
+
+
+def skip_piece_cap(length: int) -> int:
+    """Output bytes a piece of `length` bytes may write: decoded_cap(length + 3)."""
+    return int(_lib.load().b64x_skip_piece_cap(length))
+
+
+def skip_states(n: int, device="cuda") -> torch.Tensor:
+    """n states for decode_strict_skip_pieces(), each at the start of a text:
+    a zeroed uint8 tensor of n * SKIP_STATE_BYTES bytes."""
+    return torch.zeros(n * SKIP_STATE_BYTES, dtype=torch.uint8, device=device)
+
+
+def skip_pieces_layout(in_off: torch.Tensor, align: int = 4) -> torch.Tensor:
+    """Output offsets for decode_strict_skip_pieces(): npieces + 1 int64
+    entries, entry i the start of piece i's capacity (skip_piece_cap of its
+    length, the start rounded up to `align`), the last the size of the arena.
+    Like skip_batch_layout(), tensor ops on in_off's own device."""
+    return _starts((_lengths(in_off) + 6) // 4 * 3, align)
+
+
+def decode_strict_skip_pieces(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor | None,
+                              out_off: torch.Tensor | None, states: torch.Tensor,
+                              result: torch.Tensor, final: torch.Tensor | None = None,
+                              sid: torch.Tensor | None = None, skip: bytes = b"\r\n", abc=None,
+                              stream=None) -> None:
+    """decode_strict_skip() of texts that arrive in pieces, many streams in one
+    call: piece i = x[in_off[i]:in_off[i+1]] continues the text of state
+    sid[i] (an int32 tensor; None: state i) of `states` (skip_states(); the
+    indices of one call must be distinct), writes its bytes to
+    out[out_off[i]:] (skip_pieces_layout() gives the offsets) and its
+    b64x_strict_result to bytes [24 i, 24 i + 24) of `result`.  A piece with
+    final[i] & PIECE_FINAL (a uint8 tensor; None: none is) ends its text,
+    takes the whole verdict and leaves its state zeroed for the next text.
+    out None: validate only (out_off is not used).  Lengths, flags and
+    indices are read on the device: a captured call replays on others."""
+    lib = _lib.load()
+    a = _abc(abc)
+    k = _lib.skip_set(skip)
+    npieces = in_off.numel() - 1
+    _offsets(in_off, npieces + 1, "in_off")
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES * npieces:
+        raise ValueError("result must hold 24 bytes per piece")
+    _u8(x, "input")
+    _u8(states, "states")
+    if states.numel() % SKIP_STATE_BYTES or states.data_ptr() % 8:
+        raise ValueError("states must be whole 8-byte aligned states (skip_states())")
+    if sid is None:
+        if states.numel() < SKIP_STATE_BYTES * npieces:
+            raise ValueError("states must hold 128 bytes per piece")
+    elif sid.dtype != torch.int32 or not sid.is_cuda or sid.numel() < npieces:
+        raise ValueError(f"sid must be an int32 CUDA tensor of {npieces} entries")
+    if final is not None and (final.dtype != torch.uint8 or not final.is_cuda
+                              or final.numel() < npieces):
+        raise ValueError(f"final must be a uint8 CUDA tensor of {npieces} entries")
+    if out is not None:
+        _u8(out, "output")
+        _offsets(out_off, npieces, "out_off")
+    # an empty tensor has no address; nothing is read or written through the stand-in
+    _lib.check("b64x_decode_strict_skip_pieces", lib.b64x_decode_strict_skip_pieces(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), npieces,
+        None if out is None else (_ptr(out) if out.numel() else _ptr(in_off)),
+        None if out is None else _ptr(out_off), _ptr(states) if states.numel() else None,
+        _ptr(sid), _ptr(final), _ptr(result), ctypes.byref(a), ctypes.byref(k), _stream(stream)))
 
 
 def release_stream(stream=None) -> None:

@@ -538,6 +538,85 @@ int b64x_decode_strict_skip_strided(const void *d_in, uint64_t in_stride, uint64
                                     b64x_strict_result *d_res /* nbuf */,
                                     const b64x_alphabet *abc, const b64x_skip *skip, void *stream);
 
+/* Texts that arrive in pieces: the strict skip decode, continued from block
+ * to block.  Many streams go in one launch; each has a state in device memory
+ * and contributes one piece, read once by the wave that owns it.  Added
+ * within ABI 7 (symbols only).
+ *
+ * State.  Its contents are the library's own.  128 bytes of zero mean "start
+ * of a text", so a caller arms states with a memset.  Piece i continues the
+ * text of state d_state[d_sid ? d_sid[i] : i]; the state indices of one call
+ * must be distinct (not checked), and the order between calls is stream
+ * order.  A piece with d_flags[i] & B64X_PIECE_FINAL ends its text and leaves
+ * the state all zero again, ready for the next text.
+ *
+ * The result is what the scalar procedure of b64x_decode_strict_skip_dev
+ * gives for the concatenation T of the pieces one state has taken so far:
+ *  1. Every piece adds its kept bytes to the state's totals (E, the count c
+ *     of pad characters, the lowest offset of a stranger and of a pad
+ *     character, the last three kept bytes with their offsets; offsets are
+ *     offsets in T).  With npad the pad characters T ends in so far (0..2; 0
+ *     without pad): if c > npad and the first pad character lies below the
+ *     first stranger the record is {0, first_pad, PAD}; otherwise, with a
+ *     stranger, {0, first_char, CHAR}.  Such an early report is final -- PAD
+ *     and CHAR can only become more true as T grows -- and the state keeps
+ *     it: every later piece of that text gets the same record, writes no
+ *     output and need not be read (no more than its first pass of 1,024 bytes
+ *     is loaded, and nothing of it is looked at).
+ *  2. A piece that is not final, without an offence: k = the sextets carried
+ *     (0..3) plus the piece's data characters; it writes the 3 floor(k/4)
+ *     bytes of the whole groups, keeps k mod 4 sextets in the state, and its
+ *     record is {3 floor(k/4), 0, OK}.
+ *  3. A final piece without an offence so far judges LENGTH (err_pos = |T|),
+ *     then BITS (at the offset in T of kept byte D-1, which may lie in an
+ *     earlier piece); if accepted it writes the whole groups and the 1 or 2
+ *     bytes of the last partial group.  out_len is the bytes this piece
+ *     wrote: over all pieces the written bytes, concatenated, are exactly the
+ *     bytes b64x_decode_strict_skip_dev gives for T, and the out_len values
+ *     sum to its out_len.
+ *  4. An empty piece is valid: one that is not final changes nothing, a final
+ *     one finishes the text.  A piece of skipped bytes only likewise.
+ *
+ * Piece i is d_in[d_in_off[i] .. d_in_off[i+1]) and writes at d_out +
+ * d_out_off[i], capacity b64x_skip_piece_cap(len_i) = b64x_decoded_cap(len_i
+ * + 3): a final piece of 4 characters behind a carry of 3 writes 5 bytes.
+ * Nothing is written outside the capacities, the records and the states
+ * named; nothing is read outside the pieces and the states named, the wide
+ * loads at an unaligned piece's edges included.  With an offence the output
+ * bytes inside the capacity are unspecified.  Input and output must not
+ * overlap; any alignment is accepted; offsets and |T| are 64-bit.
+ * Checked in this order: npieces == 0 returns 0; a NULL d_in, d_in_off,
+ * d_state or d_res, or records or states not 8-byte aligned, -EINVAL; with
+ * d_out not NULL a NULL d_out_off -EINVAL; the skip-set rules of
+ * b64x_decode_strict_skip_dev; the alphabet rules of b64x_decode_strict_dev;
+ * then -ENODEV without a gfx950 device.
+ * Asynchronous and capture-safe: lengths, flags and state indices are read on
+ * the device, grid and kernel arguments depend on npieces, abc and skip only,
+ * so a captured call replays on other lengths, flags and indices.  No
+ * workspace, no allocation, no library state, no memset node, no atomic.
+ * Known limit: one wave walks one piece, so a piece of many MiB is exact but
+ * runs at one wave's rate, as with every batch call here.
+ * The encode side needs no such call: a caller who cuts the input at
+ * multiples of 3 L/4 bytes and sets B64X_LINES_TRAILING gets a continuable
+ * b64x_encode_lines_*. */
+#define B64X_SKIP_STATE_BYTES 128
+typedef struct b64x_skip_state {
+    uint64_t w[16];
+} b64x_skip_state; /* device memory, 8-byte aligned */
+#define B64X_PIECE_FINAL 1u
+
+/* Output capacity of a piece of len bytes: b64x_decoded_cap(len + 3). */
+uint64_t b64x_skip_piece_cap(uint64_t len);
+
+int b64x_decode_strict_skip_pieces(const void *d_in, const uint64_t *d_in_off, uint32_t npieces,
+                                   void *d_out /* NULL: validate only */,
+                                   const uint64_t *d_out_off /* npieces */,
+                                   b64x_skip_state *d_state,
+                                   const uint32_t *d_sid /* NULL: piece i continues state i */,
+                                   const uint8_t *d_flags /* NULL: no piece is final */,
+                                   b64x_strict_result *d_res /* npieces */,
+                                   const b64x_alphabet *abc, const b64x_skip *skip, void *stream);
+
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 
 typedef struct b64x_session b64x_session;

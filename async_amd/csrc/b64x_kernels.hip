@@ -4319,6 +4319,60 @@ EncChoice encode_choice(uintptr_t in, uint64_t in_stride, uint64_t len, uint32_t
     return c;
 }
 
+// Which kernels b64x_decode_strided launches.
+enum DecRoute : int {
+    kDecNothing = 0,  // nothing to decode: no launch
+    kDecRagged = 1,   // k_decode_batch_fast + k_decode_batch_fix2 (launch_batch_decode)
+    kDecRows = 2,     // k_rows_prep, k_decode_rows_lines<U, O32>, k_rows_finish
+    kDecSlots = 3,    // k_decode_slots + k_decode_batch_fix2
+};
+
+struct DecChoice {
+    int route;       // a DecRoute, or -EINVAL
+    bool o32;        // kDecRows: k_decode_rows_lines<U, true>
+    uint32_t magic;  // kDecRows: ceil(2^32 / S)
+};
+
+// The launcher's decision, from the addresses and the shape alone (host
+// arithmetic, no HIP call).  kDecRows still needs a library workspace; a
+// call that cannot have one (-EBUSY) takes kDecSlots.
+DecChoice decode_choice(uintptr_t in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                        uintptr_t out, uint64_t out_stride)
+{
+    DecChoice c = {kDecNothing, false, 0};
+    if (nbuf == 0) return c;
+    c.route = -EINVAL;
+    if (!in || !out) return c;
+    if (nbuf > 1 && (in_stride < len || out_stride < b64x_decoded_cap(len))) return c;
+    const uint64_t S = (len + 15) / 16;
+    const uint64_t slots = S * nbuf;
+    c.route = kDecRagged;
+    if (slots > 0xFFFFFFFFull - 4096 || len > 0xFFFFFFFFull) return c;
+    // any other layout: one lane per (buffer, 16-character slot)
+    c.route = kDecSlots;
+    const bool rows = nbuf >= 2 && S >= 2 && out_stride >= 12 * S && (in_stride & 3) == 0 &&
+                      (out_stride & 3) == 0 && (in & 3) == 0 && (out & 3) == 0;
+    if (!rows || S >= (1u << 20)) return c;
+    // rows with room: k_decode_rows_lines splits rel < S + U * kThreads with
+    // a multiply-high by magic = (2^32 + e) / S, exact while rel * e < 2^32;
+    // a block's rows start within 2^40 bytes of its first; the failure
+    // bitmap and the model fit the workspace's scratch
+    const uint32_t magic = (uint32_t) ((0xFFFFFFFFull + S) / S);
+    const uint64_t e = (uint64_t) magic * S - (1ull << 32);
+    const uint64_t relmax = S + (uint64_t) kRowsU * kThreads;
+    const uint64_t bitmap = ((uint64_t) nbuf + 63) / 64 * 8 + sizeof(RowModel);
+    if (!(relmax * e < (1ull << 32) && (relmax / S + 1) * in_stride < (1ull << 40) &&
+          bitmap <= b64x_decode_workspace_size(0) - kWsScratch))
+        return c;
+    c.route = kDecRows;
+    c.magic = magic;
+    // 32-bit offsets within a block's rows (relmax / S + 1 rows at most)
+    const uint64_t brows = relmax / S + 1;
+    c.o32 = in_stride < (1u << 24) && out_stride < (1u << 24) &&
+            brows * in_stride < (1ull << 31) && brows * out_stride < (1ull << 31);
+    return c;
+}
+
 // k_encode's grid is capped at the blocks the device holds at once.
 uint64_t encode_grid_cap(const DeviceInfo *d) { return (uint64_t) d->cus * d->enc_blocks_per_cu; }
 
@@ -4907,38 +4961,32 @@ int b64x_decode_strided(const void *d_in, uint64_t in_stride, uint64_t len,
                         uint64_t *d_outlen, const b64x_alphabet *abc, void *stream)
 {
     if (nbuf == 0) return 0;
-    if (!d_in || !d_out || !d_outlen) return -EINVAL;
-    if (nbuf > 1 && (in_stride < len || out_stride < b64x_decoded_cap(len))) return -EINVAL;
+    if (!d_outlen) return -EINVAL;
+    const DecChoice c = decode_choice((uintptr_t) d_in, in_stride, len, nbuf, (uintptr_t) d_out,
+                                      out_stride);
+    if (c.route < 0) return c.route;
     const uint64_t S = (len + 15) / 16;
     const uint64_t slots = S * nbuf;
     BatchLayout L{nullptr, nullptr, in_stride, out_stride, len, 0, nullptr};
-    if (slots > 0xFFFFFFFFull - 4096 || len > 0xFFFFFFFFull)
+    if (c.route == kDecRagged)
         return launch_batch_decode(d_in, L, nbuf, d_out, d_outlen, abc, stream);
     const DeviceInfo *d = device_info();
     if (!d) return -ENODEV;
     hipStream_t s = (hipStream_t) stream;
     const DecAlpha a = dec_alpha(abc);
-    const bool rows = nbuf >= 2 && S >= 2 && out_stride >= 12 * S && (in_stride & 3) == 0 &&
-                      (out_stride & 3) == 0 && (((uintptr_t) d_in) & 3) == 0 &&
-                      (((uintptr_t) d_out) & 3) == 0;
     bool done = false;
     int err = 0;
-    if (rows && S < (1u << 20)) {
+    if (c.route == kDecRows) {
         // rows with room: k_rows_prep (the failure bitmap, the line model
         // and the shape of row 0's last slot), k_decode_rows_lines (clean
         // rows by k_decode_rows2's path, MIME-formatted rows by the model),
         // k_rows_finish (every row's length; the marked rows exactly)
         constexpr uint32_t U = kRowsU;
-        const uint32_t magic = (uint32_t) ((0xFFFFFFFFull + S) / S);
-        const uint64_t e = (uint64_t) magic * S - (1ull << 32);
-        const uint64_t relmax = S + (uint64_t) U * kThreads;
+        const uint32_t magic = c.magic;
         void *ws = nullptr;
         int slot = -1;
         RowsShape held{};
-        const uint64_t bitmap = ((uint64_t) nbuf + 63) / 64 * 8 + sizeof(RowModel);
-        if (relmax * e < (1ull << 32) && (relmax / S + 1) * in_stride < (1ull << 40) &&
-            bitmap <= b64x_decode_workspace_size(0) - kWsScratch &&
-            (ws = library_workspace(stream, &slot, &err, &held))) {
+        if ((ws = library_workspace(stream, &slot, &err, &held))) {
             const uint64_t m64 = ~0ull / S + 1;
             const uint64_t per = (uint64_t) U * kThreads;
             const uint64_t tail_slot = (uint64_t) S * (nbuf - 1);
@@ -4968,12 +5016,8 @@ int b64x_decode_strided(const void *d_in, uint64_t in_stride, uint64_t len,
             // + S blocks: the row-group mapping rounds the rows up to whole
             // bands of U Ru rows (NB <= S blocks each); spare blocks return
             const dim3 g((uint32_t) ((slots + per - 1) / per + S));
-            // 32-bit offsets within a block's rows (relmax / S + 1 rows at most)
-            const uint64_t brows = relmax / S + 1;
-            const bool o32 = in_stride < (1u << 24) && out_stride < (1u << 24) &&
-                             brows * in_stride < (1ull << 31) && brows * out_stride < (1ull << 31);
-            hipLaunchKernelGGL((o32 ? k_decode_rows_lines<U, true> : k_decode_rows_lines<U, false>),
-                               g, dim3(kThreads), 0, s,
+            hipLaunchKernelGGL((c.o32 ? k_decode_rows_lines<U, true>
+                                      : k_decode_rows_lines<U, false>), g, dim3(kThreads), 0, s,
                                (const uint8_t *) d_in, in_stride, (uint32_t) len, (uint8_t *) d_out,
                                out_stride, (uint32_t) S, magic, m64, slots, tail_slot, a, nbuf, ws,
                                (const RowModel *) rm);
@@ -5291,6 +5335,43 @@ int64_t b64x__test_encode_grid_cap(void)
 {
     const DeviceInfo *d = device_info();
     return d ? (int64_t) encode_grid_cap(d) : -ENODEV;
+}
+
+// Test builds only: the route decode_choice takes for a call of
+// b64x_decode_strided with these addresses and this shape -- 0 nothing, 1
+// the ragged kernels, 2 the rows trio (k_rows_prep, k_decode_rows_lines,
+// k_rows_finish), 3 k_decode_slots + the fix-up, or -EINVAL -- and, for 2,
+// whether k_decode_rows_lines is launched with O32.  No HIP call.
+int b64x__test_decode_rows_path(uint64_t in, uint64_t in_stride, uint64_t len, uint32_t nbuf,
+                                uint64_t out, uint64_t out_stride, int *o32)
+{
+    const DecChoice c = decode_choice((uintptr_t) in, in_stride, len, nbuf, (uintptr_t) out,
+                                      out_stride);
+    if (o32) *o32 = c.o32 ? 1 : 0;
+    return c.route;
+}
+
+// Test builds only: waits for `stream`, then copies the RowModel its
+// library workspace holds (row_model_of: what the last row batch's
+// k_decode_rows_lines read) to out[96].  -ENOENT: the stream holds no
+// library workspace on the current device.
+int b64x__test_rows_model(void *stream, void *out)
+{
+    if (!out) return -EINVAL;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -ENODEV;
+    void *ws = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        for (int i = 0; i < kWsCache; i++) {
+            const WsEntry &e = g_ws[i];
+            if (e.ws && e.dev == dev && e.bound && e.stream == stream && !e.release) ws = e.ws;
+        }
+    }
+    if (!ws) return -ENOENT;
+    int err = hip_err(hipStreamSynchronize((hipStream_t) stream));
+    if (err) return err;
+    return hip_err(hipMemcpy(out, row_model_of(ws), sizeof(RowModel), hipMemcpyDeviceToHost));
 }
 #endif
 

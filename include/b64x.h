@@ -209,7 +209,11 @@ int b64x_encode_strided(const void *d_in, uint64_t in_stride, uint64_t len,
  * (out_stride >= 12*ceil(len/16)) use the stream's library workspace (as
  * b64x_decode_dev with d_workspace NULL) to hold the batch's line model;
  * when none can be had (all pinned, or a capture on a stream holding none)
- * the batch takes the general path, same bytes. */
+ * the batch takes the general path, same bytes.  In a row with room the
+ * bytes from d_outlen[i] up to min(out_stride, 12*ceil(len/16)) are scratch
+ * (whole 12-byte slots are stored, and slack up to the stride is filled);
+ * on the general path those up to b64x_decoded_cap(len) are; nothing else
+ * outside a buffer's d_outlen[i] bytes is written. */
 int b64x_decode_strided(const void *d_in, uint64_t in_stride, uint64_t len,
                         uint32_t nbuf, void *d_out, uint64_t out_stride,
                         uint64_t *d_outlen, const b64x_alphabet *abc,

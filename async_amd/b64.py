@@ -38,6 +38,10 @@ buffers and batches instead of a pull-model stream:
                                in device memory (b64x_decode_strict_skip_pieces)
     skip_states / skip_pieces_layout           its zeroed states and its output
                                offsets; SKIP_STATE_BYTES, PIECE_FINAL
+    decode_strict_skip_piece                   one large piece of one text on the
+                               same state, a wave per tile of it
+                                          (b64x_decode_strict_skip_piece_dev)
+    strict_skip_piece_workspace_size           its workspace
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
 missing or a call fails; nothing here computes base64 on the CPU.
@@ -690,6 +694,52 @@ def decode_strict_skip_pieces(x: torch.Tensor, in_off: torch.Tensor, out: torch.
         None if out is None else (_ptr(out) if out.numel() else _ptr(in_off)),
         None if out is None else _ptr(out_off), _ptr(states) if states.numel() else None,
         _ptr(sid), _ptr(final), _ptr(result), ctypes.byref(a), ctypes.byref(k), _stream(stream)))
+
+
+def strict_skip_piece_workspace_size(length: int, validate_only: bool = False) -> int:
+    """Workspace bytes decode_strict_skip_piece() needs for a piece of `length` bytes."""
+    return int(_lib.load().b64x_strict_skip_piece_workspace_size(length, validate_only))
+
+
+def decode_strict_skip_piece(x: torch.Tensor, state: torch.Tensor, result: torch.Tensor,
+                             out: torch.Tensor | None = None, final: bool = False,
+                             skip: bytes = b"\r\n", abc=None,
+                             workspace: torch.Tensor | None = None, stream=None) -> None:
+    """decode_strict_skip_pieces() of one piece, spread over the GPU: x continues
+    the text of `state` (one state of skip_states(), 128 bytes), writes its
+    bytes to `out` (at least skip_piece_cap(len) bytes; None: validate only)
+    and its b64x_strict_result to the first 24 bytes of `result`.  final: the
+    piece ends its text, takes the whole verdict and leaves the state zeroed.
+    The two calls may take turns on one state.  workspace:
+    strict_skip_piece_workspace_size(len, out is None) bytes, 8-byte aligned,
+    no preparation; allocated here when None.  A captured call replays on the
+    same length only."""
+    lib = _lib.load()
+    a = _abc(abc)
+    k = _lib.skip_set(skip)
+    _u8(x, "input")
+    n = x.numel()
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES:
+        raise ValueError("result too small")
+    _u8(state, "state")
+    if state.numel() != SKIP_STATE_BYTES or state.data_ptr() % 8:
+        raise ValueError("state must be one 8-byte aligned state (skip_states(1))")
+    if out is not None:
+        _u8(out, "output")
+        if out.numel() < skip_piece_cap(n):
+            raise ValueError("output too small")
+    need = strict_skip_piece_workspace_size(n, out is None)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    _u8(workspace, "workspace")
+    if workspace.numel() < need or workspace.data_ptr() % 8:
+        raise ValueError("workspace too small or not 8-byte aligned")
+    # an empty tensor has no address; nothing is read or written through the stand-in
+    _lib.check("b64x_decode_strict_skip_piece_dev", lib.b64x_decode_strict_skip_piece_dev(
+        _ptr(x) if n else _ptr(result), n, None if out is None else _ptr(out), _ptr(state),
+        PIECE_FINAL if final else 0, _ptr(result), ctypes.byref(a), ctypes.byref(k),
+        _ptr(workspace), _stream(stream)))
 
 
 def release_stream(stream=None) -> None:

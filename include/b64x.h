@@ -599,7 +599,8 @@ int b64x_decode_strict_skip_strided(const void *d_in, uint64_t in_stride, uint64
  * so a captured call replays on other lengths, flags and indices.  No
  * workspace, no allocation, no library state, no memset node, no atomic.
  * Known limit: one wave walks one piece, so a piece of many MiB is exact but
- * runs at one wave's rate, as with every batch call here.
+ * runs at one wave's rate, as with every batch call here: such a piece belongs
+ * on b64x_decode_strict_skip_piece_dev below, which continues the same state.
  * The encode side needs no such call: a caller who cuts the input at
  * multiples of 3 L/4 bytes and sets B64X_LINES_TRAILING gets a continuable
  * b64x_encode_lines_*. */
@@ -620,6 +621,63 @@ int b64x_decode_strict_skip_pieces(const void *d_in, const uint64_t *d_in_off, u
                                    const uint8_t *d_flags /* NULL: no piece is final */,
                                    b64x_strict_result *d_res /* npieces */,
                                    const b64x_alphabet *abc, const b64x_skip *skip, void *stream);
+
+/* One large piece of one text, spread over the GPU.  The call does what
+ * b64x_decode_strict_skip_pieces does for npieces == 1 with the piece
+ * d_in[0 .. len), the state d_state[0], d_out_off[0] == 0 and d_flags[0] ==
+ * flags: the same record, and the same bytes at d_out with capacity
+ * b64x_skip_piece_cap(len).  A final piece on a zeroed state is
+ * b64x_decode_strict_skip_dev without the lenient decoder.  Added within ABI 7
+ * (symbols only).
+ * A state that holds a report repeats it: nothing of the piece is looked at
+ * and nothing is written except the record, the first 8 bytes of the
+ * workspace and, for a final piece, the zeroed state.  The two calls may be
+ * interleaved on one state in any order: after a piece that is not final and
+ * has no offence, state words 0 to 10 are byte for byte what the pieces call
+ * leaves in the same mode (decoding or validate only; the pieces call keeps
+ * the carried sextets in a decoding call only, so a text stays in one mode),
+ * words 11 to 15 stay zero; after a piece that reports PAD or CHAR words 9 and
+ * 10 hold the report, which is all either call reads of such a state; after a
+ * final piece all 16 words are zero.
+ * Three launches in stream order -- a count pass with a wave per tile of the
+ * piece, a scan of the tiles' records with the verdict and the new state in
+ * one workgroup, a decode pass with a wave per tile (not with d_out NULL) --
+ * and no hand-off between workgroups inside one.  The text is read twice by a
+ * decoding call and once by a validate-only one.
+ * len is a host value and the grid depends on it, so a captured call replays
+ * on the same length (and the same address modulo 16) only, with any
+ * contents, state and flags' outcome; b64x_decode_strict_skip_batch and the
+ * pieces call remain the ones that replay on other lengths.
+ * d_workspace: b64x_strict_skip_piece_workspace_size(len, d_out == NULL)
+ * bytes of device memory, 8-byte aligned, one per stream.  It needs no
+ * preparation: every word the call reads it wrote earlier in the same call.
+ * The size is a head of 64 bytes and 64 bytes per tile, at most 1 MiB + 64;
+ * today it is the same for both modes.
+ * Asynchronous and capture-safe: no allocation, no synchronisation, no
+ * library state, no memset node, no global atomic.  Any alignment of the text
+ * and the output is accepted; no 32-bit limit on len.  Nothing outside [d_in,
+ * d_in + len) and the state is read, the wide loads at unaligned edges
+ * included; nothing outside the output capacity, the record, the state and
+ * the workspace is written.  With an offence the decode pass does not run and
+ * the output is untouched.  Input and output must not overlap.  The scan
+ * walks back from the end of the piece to its last three kept bytes 1,024
+ * bytes at a time in one wave, as b64x_decode_strict_skip_dev does: a piece
+ * that ends in a very long run of skipped bytes is exact but is walked at
+ * that one wave's rate.
+ * Checked in this order: a NULL d_in, d_state, d_res or d_workspace, or a
+ * record, state or workspace not 8-byte aligned, -EINVAL -- d_out may be NULL,
+ * and len == 0 still wants a d_in; flags with a bit other than
+ * B64X_PIECE_FINAL -EINVAL; the skip-set rules of
+ * b64x_decode_strict_skip_dev; the alphabet rules of b64x_decode_strict_dev;
+ * then -ENODEV without a gfx950 device. */
+uint64_t b64x_strict_skip_piece_workspace_size(uint64_t len, bool validate_only);
+
+int b64x_decode_strict_skip_piece_dev(const void *d_in, uint64_t len,
+                                      void *d_out /* NULL: validate only */,
+                                      b64x_skip_state *d_state, unsigned flags /* B64X_PIECE_FINAL */,
+                                      b64x_strict_result *d_res,
+                                      const b64x_alphabet *abc, const b64x_skip *skip,
+                                      void *d_workspace, void *stream);
 
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 

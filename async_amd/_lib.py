@@ -149,6 +149,9 @@ SIGNATURES = {
     "b64x_strict_skip_piece_workspace_size": (_u64, [_u64, ctypes.c_bool]),
     "b64x_decode_strict_skip_piece_dev": (_int, [_vp, _u64, _vp, _vp, ctypes.c_uint, _vp, _ap, _sp,
                                                  _vp, _vp]),
+    "b64x_strict_skip_pieces_wide_workspace_size": (_u64, [_u64, _u32, ctypes.c_bool]),
+    "b64x_decode_strict_skip_pieces_wide": (_int, [_vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _ap, _sp, _vp, _vp]),
     "b64x_session_open": (_vp, [_u64]),
     "b64x_session_close": (None, [_vp]),
     "b64x_session_acquire": (_vp, [_u64]),

@@ -42,6 +42,10 @@ buffers and batches instead of a pull-model stream:
                                same state, a wave per tile of it
                                           (b64x_decode_strict_skip_piece_dev)
     strict_skip_piece_workspace_size           its workspace
+    decode_strict_skip_pieces_wide             many pieces of any size in one call, a
+                               wave per tile of each, every length read on the
+                               device        (b64x_decode_strict_skip_pieces_wide)
+    strict_skip_pieces_wide_workspace_size     its workspace; STRICT_BOUND
 
 Every function raises (B64xError / RuntimeError) if the HIP library is
 missing or a call fails; nothing here computes base64 on the CPU.
@@ -59,6 +63,7 @@ from ._lib import (PIECE_FINAL, RES_BYTES, SKIP_STATE_BYTES, STRICT_RES_BYTES,  
 
 HOLD_TAIL = 1  # B64X_DEC_HOLD_TAIL
 EXPECT_JUNK = 2  # B64X_DEC_EXPECT_JUNK
+STRICT_BOUND = 6  # B64X_STRICT_BOUND: decode_strict_skip_pieces_wide's pieces exceed total_cap
 
 
 def _ptr(t: torch.Tensor | None) -> int | None:
@@ -740,6 +745,70 @@ def decode_strict_skip_piece(x: torch.Tensor, state: torch.Tensor, result: torch
         _ptr(x) if n else _ptr(result), n, None if out is None else _ptr(out), _ptr(state),
         PIECE_FINAL if final else 0, _ptr(result), ctypes.byref(a), ctypes.byref(k),
         _ptr(workspace), _stream(stream)))
+
+
+def strict_skip_pieces_wide_workspace_size(total_cap: int, npieces: int,
+                                           validate_only: bool = False) -> int:
+    """Workspace bytes decode_strict_skip_pieces_wide() needs for npieces pieces
+    of at most total_cap bytes together."""
+    return int(_lib.load().b64x_strict_skip_pieces_wide_workspace_size(total_cap, npieces,
+                                                                       validate_only))
+
+
+def decode_strict_skip_pieces_wide(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor | None,
+                                   out_off: torch.Tensor | None, states: torch.Tensor,
+                                   result: torch.Tensor, workspace: torch.Tensor,
+                                   total_cap: int | None = None, sid: torch.Tensor | None = None,
+                                   flags: torch.Tensor | None = None, skip: bytes = b"\r\n",
+                                   abc=None, stream=None) -> None:
+    """decode_strict_skip_pieces() with a wave on every tile of every piece:
+    the same pieces, states, records and bytes, for pieces of any size in a
+    constant number of launches.  total_cap (default x.numel()) bounds
+    in_off[-1] - in_off[0] and is the only length the host sees, so a captured
+    call replays on other lengths, flags and indices within it; pieces that
+    exceed it get the record {0, their bytes, STRICT_BOUND} and nothing is
+    looked at.  flags: a uint8 tensor, flags[i] & PIECE_FINAL ends text i
+    (None: none is).  A piece with an offence writes nothing to `out`.
+    workspace: strict_skip_pieces_wide_workspace_size(total_cap, npieces,
+    out is None) bytes, 8-byte aligned, no preparation."""
+    lib = _lib.load()
+    a = _abc(abc)
+    k = _lib.skip_set(skip)
+    npieces = in_off.numel() - 1
+    _offsets(in_off, npieces + 1, "in_off")
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES * npieces:
+        raise ValueError("result must hold 24 bytes per piece")
+    _u8(x, "input")
+    if total_cap is None:
+        total_cap = x.numel()
+    if total_cap < 0:
+        raise ValueError("total_cap must not be negative")
+    _u8(states, "states")
+    if states.numel() % SKIP_STATE_BYTES or states.data_ptr() % 8:
+        raise ValueError("states must be whole 8-byte aligned states (skip_states())")
+    if sid is None:
+        if states.numel() < SKIP_STATE_BYTES * npieces:
+            raise ValueError("states must hold 128 bytes per piece")
+    elif sid.dtype != torch.int32 or not sid.is_cuda or sid.numel() < npieces:
+        raise ValueError(f"sid must be an int32 CUDA tensor of {npieces} entries")
+    if flags is not None and (flags.dtype != torch.uint8 or not flags.is_cuda
+                              or flags.numel() < npieces):
+        raise ValueError(f"flags must be a uint8 CUDA tensor of {npieces} entries")
+    if out is not None:
+        _u8(out, "output")
+        _offsets(out_off, npieces, "out_off")
+    _u8(workspace, "workspace")
+    need = strict_skip_pieces_wide_workspace_size(total_cap, npieces, out is None)
+    if workspace.numel() < need or workspace.data_ptr() % 8:
+        raise ValueError("workspace too small or not 8-byte aligned")
+    # an empty tensor has no address; nothing is read or written through the stand-in
+    _lib.check("b64x_decode_strict_skip_pieces_wide", lib.b64x_decode_strict_skip_pieces_wide(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), npieces, total_cap,
+        None if out is None else (_ptr(out) if out.numel() else _ptr(in_off)),
+        None if out is None else _ptr(out_off), _ptr(states) if states.numel() else None,
+        _ptr(sid), _ptr(flags), _ptr(result), ctypes.byref(a), ctypes.byref(k), _ptr(workspace),
+        _stream(stream)))
 
 
 def release_stream(stream=None) -> None:

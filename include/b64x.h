@@ -679,6 +679,68 @@ int b64x_decode_strict_skip_piece_dev(const void *d_in, uint64_t len,
                                       const b64x_alphabet *abc, const b64x_skip *skip,
                                       void *d_workspace, void *stream);
 
+/* Many pieces of any size in one call: b64x_decode_strict_skip_pieces with a
+ * wave on every tile of every piece, as b64x_decode_strict_skip_piece_dev puts
+ * one on every tile of its piece, in a constant number of launches.  Added
+ * within ABI 7 (symbols only).
+ * For every piece the record, the bytes written at d_out + d_out_off[i]
+ * (capacity b64x_skip_piece_cap(len_i)) and the state left behind are those of
+ * b64x_decode_strict_skip_pieces with the same arguments: state words 0 to 10
+ * byte for byte the same in the same mode, words 11 to 15 zero, all 16 zero
+ * after a final piece; after a piece that reports PAD or CHAR words 9 and 10
+ * hold the report, which is all any of the calls reads of such a state.  The
+ * three calls may take turns on one state in any order.  A state that holds a
+ * report repeats it and nothing of that piece is looked at: no more than the
+ * first pass of 1,024 bytes of each of its tiles is loaded, as the pieces call
+ * loads a piece's first pass before it knows the state.  Stronger than the pieces call: a piece whose record carries an
+ * offence, held or new, writes nothing to its output -- the decode pass runs
+ * behind the verdict.
+ * total_cap is a host bound on d_in_off[npieces] - d_in_off[0]; the size of
+ * the caller's text buffer will do.  It is the only length the host sees: tile
+ * size, grids, kernel arguments and workspace size are functions of total_cap,
+ * npieces, abc, skip and d_out == NULL alone, so a captured call replays on
+ * other lengths, flags, state indices and contents within the same bound.  If
+ * the device finds d_in_off[npieces] - d_in_off[0] > total_cap, no piece is
+ * looked at, no state and no output byte is touched, and every record is
+ * {0, d_in_off[npieces] - d_in_off[0], B64X_STRICT_BOUND}.
+ * Four launches in stream order (three with d_out NULL): a prefix over the
+ * pieces' tile counts in one workgroup, which also maps every tile to its
+ * piece; a count pass with a wave per tile; a scan per piece -- a wave for a
+ * piece of up to 64 tiles, a workgroup for a longer one -- with the verdict
+ * and the new state; a decode pass with a wave per tile.  The text is read
+ * twice by a decoding call and once by a validate-only one, so a batch of
+ * single-tile pieces is cheaper on b64x_decode_strict_skip_pieces.
+ * d_workspace: b64x_strict_skip_pieces_wide_workspace_size(total_cap, npieces,
+ * d_out == NULL) bytes of device memory, 8-byte aligned, one per stream, no
+ * preparation: 64 bytes per piece, 72 bytes per tile of the bound
+ * ceil(total_cap / T) + 2 npieces, and small change.
+ * Any alignment of text and output; 64-bit offsets and |T|; input and output
+ * must not overlap; the state indices of one call are distinct (not checked).
+ * Nothing outside the pieces, states and workspace is read, the wide loads at
+ * unaligned edges included; nothing outside capacities, records, states and
+ * workspace is written.  Asynchronous and capture-safe: no allocation, no
+ * synchronisation, no library state, no memset node, no global atomic, no spin
+ * or hand-off between workgroups inside a launch.
+ * Checked in this order: npieces == 0 returns 0; a NULL d_in, d_in_off,
+ * d_state, d_res or d_workspace, or records, states or workspace not 8-byte
+ * aligned, -EINVAL; with d_out not NULL a NULL d_out_off -EINVAL; the skip-set
+ * rules of b64x_decode_strict_skip_dev; the alphabet rules of
+ * b64x_decode_strict_dev; then -ENODEV without a gfx950 device. */
+#define B64X_STRICT_BOUND 6u  /* the call's pieces are longer than the bound the caller gave; nothing was looked at */
+
+uint64_t b64x_strict_skip_pieces_wide_workspace_size(uint64_t total_cap, uint32_t npieces, bool validate_only);
+
+int b64x_decode_strict_skip_pieces_wide(const void *d_in, const uint64_t *d_in_off, uint32_t npieces,
+                                        uint64_t total_cap,
+                                        void *d_out /* NULL: validate only */,
+                                        const uint64_t *d_out_off /* npieces */,
+                                        b64x_skip_state *d_state,
+                                        const uint32_t *d_sid /* NULL: piece i continues state i */,
+                                        const uint8_t *d_flags /* NULL: no piece is final */,
+                                        b64x_strict_result *d_res /* npieces */,
+                                        const b64x_alphabet *abc, const b64x_skip *skip,
+                                        void *d_workspace, void *stream);
+
 /* ---- host-memory sessions (used by the bytestream_1 stages) ----------- */
 
 typedef struct b64x_session b64x_session;

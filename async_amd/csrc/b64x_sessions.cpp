@@ -598,8 +598,9 @@ int b64x_lane_encode_async(b64x_lane *l, const uint8_t *h_in, uint32_t njobs,
     if (njobs) {
         const uint64_t words = (uint64_t) njobs + 1;
         const uint64_t in_bytes = h_in_off[njobs];
-        for (uint32_t i = 0; i < nseg; i++)  // sorted, inside the batch
-            if (h_seg[i].off + h_seg[i].len > in_bytes || (i && h_seg[i].off < h_seg[i - 1].off + h_seg[i - 1].len))
+        for (uint32_t i = 0; i < nseg; i++)  // sorted, inside the batch (off + len may wrap)
+            if (h_seg[i].len > in_bytes || h_seg[i].off > in_bytes - h_seg[i].len ||
+                (i && h_seg[i].off < h_seg[i - 1].off + h_seg[i - 1].len))
                 return -EINVAL;
         if ((err = lane_stage_in(l, nseg ? nullptr : h_in, njobs, h_in_off, h_out_off, 0)))
             return err;

@@ -24,6 +24,9 @@ buffers and batches instead of a pull-model stream:
                                per buffer     (b64x_decode_strict_batch)
     lines_batch_layout / strict_batch_layout   their output offsets, from the
                                input offsets, on the tensor's own device
+    encode_batch_wide                          ragged batches, plain or wrapped,
+                               balanced over bytes: buffers of any size in
+                               one call       (b64x_encode_batch_wide)
     decode_strict_skip(x)      one buffer, strict, ignoring CR and LF (or another
                                small set of bytes) wherever they stand; also
                                validate-only   (b64x_decode_strict_skip_dev)
@@ -481,6 +484,35 @@ def encode_lines_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,
         _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf,
         _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), ctypes.byref(a),
         ctypes.byref(fmt), _stream(stream)))
+
+
+def encode_batch_wide(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,
+                      out_off: torch.Tensor, line_len: int | None = None, sep: bytes = b"\r\n",
+                      trailing: bool = True, total_hint: int | None = None, abc=None,
+                      stream=None) -> None:
+    """encode_batch() (line_len None) or encode_lines_batch() balanced over the
+    batch's bytes instead of its buffers: the same addressing, the same bytes
+    written, but a buffer of MiB among buffers of KiB is spread over the
+    device like the rest.  out_off is encode_batch's encoded_len layout, or
+    lines_batch_layout()'s.  total_hint sizes the grid and nothing else (None:
+    x.numel(); 0: fill the device); the lengths are read on the device, the
+    call makes no host synchronisation and replays on other offsets."""
+    lib = _lib.load()
+    a = _abc(abc)
+    nbuf = in_off.numel() - 1
+    _offsets(in_off, nbuf + 1, "in_off")
+    _offsets(out_off, nbuf, "out_off")
+    fmt, ref = _fmt(line_len, sep, trailing)  # fmt: alive until the call has read it
+    _u8(x, "input")
+    _u8(out, "output")
+    hint = x.numel() if total_hint is None else int(total_hint)
+    if hint < 0:
+        raise ValueError("total_hint must not be negative")
+    # an empty tensor has no address; nothing is read through the stand-in
+    _lib.check("b64x_encode_batch_wide", lib.b64x_encode_batch_wide(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf, hint,
+        _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), ctypes.byref(a), ref,
+        _stream(stream)))
 
 
 def decode_strict_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,

@@ -372,7 +372,8 @@ int b64x_decode_strict_strided(const void *d_in, uint64_t in_stride, uint64_t le
  * buffer's length -- but one wave walks one buffer, so a buffer of hundreds
  * of MiB, exact as it is, runs at one wave's rate (the kernels balance a
  * batch over buffers, not over the bytes of one): such a buffer belongs on
- * the one-buffer calls, as with b64x_encode_batch's one block per buffer. */
+ * the one-buffer calls, as with b64x_encode_batch's one block per buffer --
+ * or, for the encode, in a batch of b64x_encode_batch_wide below. */
 
 /* Buffer i wrapped on its own: byte for byte what b64x_encode_lines_dev()
  * writes for it under the same abc and fmt, b64x_encoded_lines_len(len_i,
@@ -403,6 +404,42 @@ int b64x_decode_strict_batch(const void *d_in, const uint64_t *d_in_off, uint32_
                              b64x_strict_result *d_res /* nbuf */,
                              const b64x_alphabet *abc, const b64x_lines *fmt /* NULL: plain */,
                              void *stream);
+
+/* The ragged encode balanced over the batch's bytes, not over its buffers:
+ * an 8 MiB buffer among 4 KiB ones is spread over the device like the rest,
+ * so the host need not look at the lengths to route the large ones to the
+ * one-buffer calls.  Added within ABI 7 (a symbol only).
+ * Buffers are addressed exactly as in b64x_encode_batch (d_in_off[0] may be
+ * nonzero; an empty buffer writes nothing).  With fmt NULL buffer i gets byte
+ * for byte what b64x_encode_batch writes for it, otherwise what
+ * b64x_encode_lines_batch writes under the same abc and fmt; nothing is
+ * written outside [d_out_off[i], d_out_off[i] + len_out_i).  Nothing is read
+ * outside the arena [d_in + d_in_off[0], d_in + d_in_off[nbuf]) and the two
+ * offset arrays, and the dword loads of a buffer's fast path stay inside that
+ * buffer.
+ * total_hint is the only length the host sees: it sizes the grid
+ * (ceil(total_hint / 48 KiB) blocks, between 1 and 8 per CU) and nothing
+ * else.  0 means "unknown: fill the device".  The result is exact for any
+ * value, too small, too large or 0: each wave reads the arena's size on the
+ * device and takes an equal span of it (at least 12 KiB), finds the span's
+ * buffers by a binary search over d_in_off, and every 16-byte output block
+ * of every buffer has exactly one owning span.  The grid and every kernel
+ * argument depend on nbuf, total_hint, abc, fmt and the device alone: a
+ * captured call replays on other offsets.
+ * One launch: no workspace, no allocation, no synchronisation, no atomic, no
+ * library state.  Any alignment of any buffer is accepted, mixed within a
+ * batch (both addresses 4-byte aligned, and L >= 16 when wrapped, is a
+ * buffer's fast path); no 32-bit limit on a buffer or on the arena.
+ * It pays a search per wave: batches of many small buffers only are served
+ * better by b64x_encode_batch / b64x_encode_lines_batch (README.md has the
+ * measured crossing).
+ * Checked in this order: nbuf == 0 returns 0, NULL pointers -EINVAL, with
+ * fmt the format rules of b64x_encode_lines_dev, then -ENODEV. */
+int b64x_encode_batch_wide(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
+                           uint64_t total_hint,
+                           void *d_out, const uint64_t *d_out_off,
+                           const b64x_alphabet *abc,
+                           const b64x_lines *fmt /* NULL: plain */, void *stream);
 
 /* ---- strict decode that skips line breaks ------------------------------ */
 

@@ -55,6 +55,7 @@ PIECES_SRC = async_amd/csrc/b64x_skip_pieces.hip
 WIDE_SRC   = async_amd/csrc/b64x_skip_wide.hip
 PW_SRC     = async_amd/csrc/b64x_skip_pieces_wide.hip
 EW_SRC     = async_amd/csrc/b64x_encode_wide.hip
+SW_SRC     = async_amd/csrc/b64x_strict_wide.hip
 # What the units of the strict decode that skips line breaks share, and the
 # walk of its two one-pass units.
 SKIP_HDRS  = async_amd/csrc/b64x_skip_body.h
@@ -65,6 +66,9 @@ WIDE_HDRS  = async_amd/csrc/b64x_skip_wide_plan.h
 PW_HDRS    = async_amd/csrc/b64x_skip_pieces_wide_plan.h $(WIDE_HDRS)
 # The plan of the ragged encode balanced over bytes (no HIP in it either).
 EW_HDRS    = async_amd/csrc/b64x_encode_wide_plan.h
+# The plan of the ragged strict decode balanced over bytes (no HIP in it
+# either; the shares' saturating arithmetic is the encode plan's).
+SW_HDRS    = async_amd/csrc/b64x_strict_wide_plan.h $(EW_HDRS)
 # Every header the line-wrapped encode, the strict decode and their ragged
 # forms include: the plan arithmetic, the common device header and the
 # per-lane bodies the one-buffer and the ragged-batch units share.
@@ -77,12 +81,12 @@ HEADERS    = $(wildcard include/*.h)
 
 HOST_OBJ   = $(patsubst async_amd/csrc/%.c,$(OBJDIR)/%.o,$(HOST_SRC))
 # The GPU side of every library next to its kernel object (b64x_kernels.o, or
-# the hooks build of it): the nine satellite code objects, in link order,
+# the hooks build of it): the ten satellite code objects, in link order,
 # and the host-only sessions unit.
 GPU_OBJ    = $(OBJDIR)/b64x_wrap.o $(OBJDIR)/b64x_strict.o $(OBJDIR)/b64x_lines_batch.o \
              $(OBJDIR)/b64x_skip.o $(OBJDIR)/b64x_skip_rows.o $(OBJDIR)/b64x_skip_pieces.o \
              $(OBJDIR)/b64x_skip_wide.o $(OBJDIR)/b64x_skip_pieces_wide.o $(OBJDIR)/b64x_encode_wide.o \
-             $(OBJDIR)/b64x_sessions.o
+             $(OBJDIR)/b64x_strict_wide.o $(OBJDIR)/b64x_sessions.o
 
 # The same harness over the product's host C with a CPU stand-in for the GPU
 # side (tests/csrc/fake_b64x.c): deterministic, adversarially ordered tests
@@ -138,6 +142,10 @@ $(OBJDIR)/b64x_skip_pieces_wide.o: $(PW_SRC) $(PW_HDRS) $(WALK_HDRS) $(SKIP_HDRS
 
 # The ragged encode balanced over bytes, plain and wrapped: likewise, linked after all nine.
 $(OBJDIR)/b64x_encode_wide.o: $(EW_SRC) $(EW_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# The ragged strict decode balanced over bytes, plain and wrapped: likewise, linked after all ten.
+$(OBJDIR)/b64x_strict_wide.o: $(SW_SRC) $(SW_HDRS) $(LINES_HDRS) $(HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: async_amd/csrc/%.c $(HEADERS) async_amd/csrc/b64_hub.h async_amd/csrc/b64_lend.h async_amd/csrc/b64_pin.h | $(OBJDIR)

@@ -140,6 +140,7 @@ SIGNATURES = {
     "b64x_encode_lines_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _ap, _lp, _vp]),
     "b64x_decode_strict_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _lp, _vp]),
     "b64x_encode_batch_wide": (_int, [_vp, _vp, _u32, _u64, _vp, _vp, _ap, _lp, _vp]),
+    "b64x_decode_strict_batch_wide": (_int, [_vp, _vp, _u32, _u64, _vp, _vp, _vp, _ap, _lp, _vp]),
     "b64x_strict_skip_workspace_size": (_u64, [_u64, ctypes.c_bool]),
     "b64x_decode_strict_skip_dev": (_int, [_vp, _u64, _vp, _vp, _ap, _sp, _vp, _vp]),
     "b64x_decode_strict_skip_batch": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _ap, _sp, _vp, _vp]),

@@ -27,6 +27,9 @@ buffers and batches instead of a pull-model stream:
     encode_batch_wide                          ragged batches, plain or wrapped,
                                balanced over bytes: buffers of any size in
                                one call       (b64x_encode_batch_wide)
+    decode_strict_batch_wide                   ragged batches, strict, balanced
+                               over bytes: texts of any size in one call, one
+                               record per text (b64x_decode_strict_batch_wide)
     decode_strict_skip(x)      one buffer, strict, ignoring CR and LF (or another
                                small set of bytes) wherever they stand; also
                                validate-only   (b64x_decode_strict_skip_dev)
@@ -537,6 +540,39 @@ def decode_strict_batch(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor
     _u8(out, "output")
     _lib.check("b64x_decode_strict_batch", lib.b64x_decode_strict_batch(
         _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf,
+        _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), _ptr(result),
+        ctypes.byref(a), ref, _stream(stream)))
+
+
+def decode_strict_batch_wide(x: torch.Tensor, in_off: torch.Tensor, out: torch.Tensor,
+                             out_off: torch.Tensor, result: torch.Tensor,
+                             line_len: int | None = None, sep: bytes = b"\r\n",
+                             trailing: bool = True, total_hint: int | None = None, abc=None,
+                             stream=None) -> None:
+    """decode_strict_batch() balanced over the batch's bytes instead of its
+    texts: the same addressing (strict_batch_layout() gives out_off), the same
+    records and, for an accepted text, the same bytes, but a text of MiB among
+    texts of KiB is spread over the device like the rest.  total_hint sizes
+    the grid and nothing else (None: x.numel(); 0: fill the device); the
+    lengths are read on the device, the call makes no host synchronisation and
+    replays on other offsets and contents."""
+    lib = _lib.load()
+    a = _abc(abc)
+    nbuf = in_off.numel() - 1
+    _offsets(in_off, nbuf + 1, "in_off")
+    _offsets(out_off, nbuf, "out_off")
+    _u8(result, "result")
+    if result.numel() < STRICT_RES_BYTES * nbuf:
+        raise ValueError("result must hold 24 bytes per buffer")
+    fmt, ref = _fmt(line_len, sep, trailing)  # fmt: alive until the call has read it
+    _u8(x, "input")
+    _u8(out, "output")
+    hint = x.numel() if total_hint is None else int(total_hint)
+    if hint < 0:
+        raise ValueError("total_hint must not be negative")
+    # an empty tensor has no address; nothing is read through the stand-in
+    _lib.check("b64x_decode_strict_batch_wide", lib.b64x_decode_strict_batch_wide(
+        _ptr(x) if x.numel() else _ptr(in_off), _ptr(in_off), nbuf, hint,
         _ptr(out) if out.numel() else _ptr(in_off), _ptr(out_off), _ptr(result),
         ctypes.byref(a), ref, _stream(stream)))
 

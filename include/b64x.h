@@ -373,7 +373,8 @@ int b64x_decode_strict_strided(const void *d_in, uint64_t in_stride, uint64_t le
  * of MiB, exact as it is, runs at one wave's rate (the kernels balance a
  * batch over buffers, not over the bytes of one): such a buffer belongs on
  * the one-buffer calls, as with b64x_encode_batch's one block per buffer --
- * or, for the encode, in a batch of b64x_encode_batch_wide below. */
+ * or in a batch of the wide calls below, b64x_encode_batch_wide and
+ * b64x_decode_strict_batch_wide. */
 
 /* Buffer i wrapped on its own: byte for byte what b64x_encode_lines_dev()
  * writes for it under the same abc and fmt, b64x_encoded_lines_len(len_i,
@@ -440,6 +441,57 @@ int b64x_encode_batch_wide(const void *d_in, const uint64_t *d_in_off, uint32_t 
                            void *d_out, const uint64_t *d_out_off,
                            const b64x_alphabet *abc,
                            const b64x_lines *fmt /* NULL: plain */, void *stream);
+
+/* The ragged strict decode balanced over the batch's bytes, not over its
+ * texts: the decode and check of what b64x_encode_batch_wide writes, an 8 MiB
+ * text among 4 KiB ones spread over the device like the rest.  Added within
+ * ABI 7 (a symbol only).
+ * Texts are addressed exactly as in b64x_decode_strict_batch (d_in_off[0] may
+ * be nonzero): text i is d_in[d_in_off[i] .. d_in_off[i+1]), its bytes go to
+ * d_out + d_out_off[i] (capacity b64x_strict_decoded_cap(len_i, fmt)), its
+ * record to d_res[i].  For every i, d_res[i] is exactly the record the scalar
+ * procedure above ("strict decode with first-error position") gives for text
+ * i alone: {0, len_i, LENGTH} where no encoder output has that length
+ * (decided per text, on the device; nothing of such a text is read),
+ * {0, 0, OK} for an empty text.  Every record is written whole: the caller
+ * prepares nothing.  An accepted text's bytes are byte for byte those of
+ * b64x_decode_strict_batch; with err != 0 the text's output bytes are
+ * unspecified but stay inside its capacity.  Nothing is written outside the
+ * capacities and the records; nothing is read outside the arena
+ * [d_in + d_in_off[0], d_in + d_in_off[nbuf]) and the two offset arrays, and
+ * the dword windows of a text's fast path stay inside that text.
+ * total_hint works as in b64x_encode_batch_wide: the only length the host
+ * sees, it sizes the grid (ceil(total_hint / 64 KiB) blocks, between 1 and 8
+ * per CU) and nothing else; 0 means "unknown: fill the device".  The result
+ * is exact for any value: each wave reads the arena's size on the device and
+ * takes an equal span of it (at least 16 KiB of text), finds the span's texts
+ * by a binary search over d_in_off, and every 16-character lane of every text
+ * belongs to the one span that holds its first character.  The grid and every
+ * kernel argument depend on nbuf, total_hint, abc, fmt and the device alone:
+ * a captured call replays on other offsets and contents.
+ * Three graph nodes whatever the sizes, after b64x_decode_strict_dev: a
+ * one-thread-per-text kernel that sets the 24 nbuf record bytes to ones (a
+ * kernel, not a memset node: a captured memset node did not keep its bytes
+ * from the second replay of a graph on), the decode kernel (a lane that finds
+ * an offence lowers the text's key with one 64-bit atomic; good text performs
+ * none) and a one-thread-per-text kernel that gives each record its final
+ * form.  No workspace, no allocation, no synchronisation, no library state.
+ * Any alignment of any text is accepted, mixed within a batch (both addresses
+ * 4-byte aligned, and L >= 16 when wrapped, is a text's fast path); no 32-bit
+ * limit on a text or on the arena.
+ * It pays a search per wave and two record kernels: batches of many
+ * texts that are all below 16 KiB are served better by
+ * b64x_decode_strict_batch, a batch that holds texts from 32 KiB up by this
+ * call (README.md has the measured crossing).
+ * Checked in this order: nbuf == 0 returns 0, NULL pointers (or a record array
+ * not 8-byte aligned) -EINVAL, with fmt the format rules of
+ * b64x_decode_strict_dev, then its alphabet rules, then -ENODEV. */
+int b64x_decode_strict_batch_wide(const void *d_in, const uint64_t *d_in_off, uint32_t nbuf,
+                                  uint64_t total_hint,
+                                  void *d_out, const uint64_t *d_out_off,
+                                  b64x_strict_result *d_res /* nbuf */,
+                                  const b64x_alphabet *abc,
+                                  const b64x_lines *fmt /* NULL: plain */, void *stream);
 
 /* ---- strict decode that skips line breaks ------------------------------ */
 
